@@ -2,7 +2,7 @@
 """Headline benchmark: ray-steps/sec of a 1e5-ray Munk fan to 1000 km (BASELINE.json configs[1]),
 plus the eigenray wall-clock of configs[3].
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
 
 With N > 1 and no WORLD_SIZE in the environment this process only LAUNCHES the N ranks (one per
 GPU, `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`,
@@ -77,7 +77,14 @@ def parse_args(argv=None):
     ap.add_argument("--waves-per-block", type=int, default=0)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; tests rehearse with gloo)")
     ap.add_argument("--launcher-only", action="store_true", help="(tests) start the ranks, let them report, do no GPU work")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float64; rank 0's rays, "
+                         "dropped rays left out as pr.shoot_rays leaves them out): per-ray end states and counters, and the "
+                         "trajectories of a fixed, seeded sample of rays")
+    args = ap.parse_args(argv)
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
+    return args
 
 
 def spawn_ranks(args, argv):
@@ -93,6 +100,50 @@ def spawn_ranks(args, argv):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", f"--nproc-per-node={args.gpus}",
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + list(argv)
     return subprocess.call(cmd, env=env)
+
+
+DUMP_RAYS = 100_000        # --dump-outputs: per-ray arrays of every ray up to this many, else of a seeded sample
+DUMP_TRAJ_RAYS = 1024      # ... and the trajectories of a seeded sample of this many rays (1024 x 1001 x 3 x 8 B = 24.6 MB)
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(fan, out_dir):
+    """`--dump-outputs`: what the fan's last pass computed, written as out_dir/<name>.npy in float64.  Like the fan
+    pr.shoot_rays returns, it holds the rays the integrator kept (status 0) only: a dropped ray's end state and
+    samples are NaN on the device and vanish from the caller's fan.  `end` (T, z, p at the receiver range), `n_bott`,
+    `n_surf`, `n_steps` and `n_rej` are per ray (rows = launch indices `ray_index`); `traj_T`, `traj_z`, `traj_p` are
+    [ray][sample] whatever the layout in HBM (rows = `traj_ray_index`).  The launch indices sampled depend on the fan
+    size alone, so runs with the same arguments compare array for array."""
+    import torch
+    kept = (fan.status == 0).cpu().numpy()
+
+    def sample(k, seed):
+        idx = np.arange(fan.N) if fan.N <= k else np.sort(np.random.default_rng(seed).choice(fan.N, k, replace=False))
+        return idx[kept[idx]]
+
+    rays = sample(DUMP_RAYS, 0)
+    ri = torch.from_numpy(rays).to(fan.dev)
+    out = {"ray_index": rays, "end": fan.end[ri], "n_bott": fan.n_bott[ri],
+           "n_surf": fan.n_surf[ri], "n_steps": fan.n_steps[ri], "n_rej": fan.n_rej[ri]}
+    if fan.save:
+        traj = sample(DUMP_TRAJ_RAYS, 1)
+        ti = torch.from_numpy(traj).to(fan.dev)
+        out["traj_ray_index"] = traj
+        for name, t in (("traj_T", fan.T), ("traj_z", fan.Z), ("traj_p", fan.P)):
+            if fan.sample_blocked:       # [ceil(S/4)][N][4]
+                out[name] = t[:, ti, :].permute(1, 0, 2).reshape(len(traj), -1)[:, :fan.S]
+            elif fan.sample_major:       # [S][N]
+                out[name] = t[:, ti].T
+            else:                        # [N][S]
+                out[name] = t[ti]
+    out = {k: np.ascontiguousarray((v.cpu().numpy() if torch.is_tensor(v) else v).astype(np.float64)) for k, v in out.items()}
+    total = sum(a.nbytes for a in out.values())
+    if total > DUMP_MAX_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_MAX_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for k, a in out.items():
+        np.save(os.path.join(out_dir, k + ".npy"), a)
+    return {"dir": out_dir, "files": sorted(k + ".npy" for k in out), "bytes": total}
 
 
 def munk_tables(r_max, nr=100, sofar_slope=0.0):
@@ -570,6 +621,7 @@ def main(argv=None):
         total_steps, n_drop = int(ss[0].item()), int(ss[1].item())
     else:
         total_steps = local_steps
+    dumped = dump_outputs(fan, args.dump_outputs) if (args.dump_outputs and rank == 0) else None
 
     # configs[3] over the ranks (every rank takes part): the fan's launch angles are dealt to the ranks, ONE all-gather
     # of the end records puts the fan on every rank, every rank brackets on the whole fan, the brackets are dealt to the
@@ -684,6 +736,8 @@ def main(argv=None):
                                     "note": "SQ_INSTS_VALU of the fan kernel (committed PMC pass) over 1024 SIMDs x 2.4 GHz / 4 "
                                             "cycles x this run's kernel time: the bound that really holds (every VALU "
                                             "instruction of the stepper is fp64 or issues at the same 4-cycle cadence)"}
+        if dumped is not None:
+            out["dump_outputs"] = dumped
         if args.histogram and hist is not None:
             out["histogram"] = {"bins": HIST_BINS, "range_s": [T_LO, T_HI], "counted_rays": int(hist.sum().item())}
         if world == 1 and not args.no_cpu_baseline:
