@@ -41,13 +41,9 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # whose own constants never fitted anyway, gets up to 3 % faster.  (Three waves per SIMD then fit,
 # but measured slower: 1e6 rays 45.0 vs 42.4 ms, 180 000 rays 13.1 vs 9.8 ms -- a workgroup holds
 # its CU until its last wave ends and the fans are VALU-bound already.)
-HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-mllvm", "-disable-machine-licm"]
-if os.environ.get("PGR_FMA"):      # experiments only: FMA contraction + 2-ulp rsqrt (breaks 1e-8 parity)
-    HIPCC_FLAGS += ["-DPGR_FMA", "-ffp-contract=fast"]
-elif os.environ.get("PGR_STRICT"):  # compiler's IEEE divide/sqrt and pow()
-    HIPCC_FLAGS += ["-DPGR_STRICT", "-ffp-contract=off"]
-else:                               # default: reference arithmetic, cheaper correctly-rounded div/sqrt
-    HIPCC_FLAGS += ["-ffp-contract=off"]
+# -ffp-contract=off: the reference's arithmetic (build_contracted() appends CONTRACTED_FLAGS, whose -ffp-contract=fast wins).
+HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-mllvm", "-disable-machine-licm",
+               "-ffp-contract=off"]
 
 PGR_TERMINATE_BACKWARDS = 1
 PGR_SAMPLE_MAJOR = 2
@@ -142,13 +138,13 @@ def _relayout(td, verbose):
 def build(force=False, verbose=False, out=None, extra_flags=()):
     """Compile csrc/pgr_hip.hip (ONE translation unit; it includes every csrc/*.h) for gfx950 (cross-compiles without a GPU): hipcc, then the
     instruction-layout pass over its assembly (_relayout; PGR_NO_RELAYOUT=1 or any failure of that
-    pass leaves the plain hipcc build in place).  `out` / `extra_flags`: build a variant library
-    somewhere else (A/B experiments, scripts/kbench.py --lib); the default builds the product."""
+    pass leaves the plain hipcc build in place).  The default builds the product, REFERENCE_LIB, whatever PGR_ARITH
+    says; `out` / `extra_flags`: build a variant library somewhere else (build_contracted(), scripts/build_variants.py)."""
     import shutil
     import tempfile
-    if out is None and ARITH == "contracted" and not extra_flags:
-        extra_flags = CONTRACTED_FLAGS      # (PGR_ARITH=contracted: `build()` builds the library this process loads)
-    LIB_PATH = out or globals()["LIB_PATH"]
+    if extra_flags and out is None:
+        raise ValueError("build(extra_flags=...) needs `out`: only the product's own recipe writes the product library")
+    LIB_PATH = out or REFERENCE_LIB
     src = os.path.join(CSRC, "pgr_hip.hip")
     hdr = os.path.join(_HERE, "..", "include", "pgr.h")
     # (one translation unit: pgr_hip.hip includes every csrc/*.h -- device building blocks, the fan kernel, the host side in pieces)

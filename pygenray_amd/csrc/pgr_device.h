@@ -6,21 +6,6 @@
 #ifndef PGR_DEVICE_H
 #define PGR_DEVICE_H
 
-#ifdef PGR_LIBM_TRIG  // experiments: the device library's asin / sin / pow at bounces (NOT bit-identical)
-#define pgr_cr_asin(x) asin(x)
-#define pgr_cr_sin(x) sin(x)
-#define pgr_cr_pow_p02(x) pow((x), 0.2)
-#define PGR_ASIN_DD_T double
-#define PGR_ASIN_DD(v) asin(v)
-#define PGR_ASIN_DD_HI(a) (a)
-#define PGR_SIN_REFLECT(x, v, a) sin(x)
-#else
-#define PGR_ASIN_DD_T struct pgr_dd
-#define PGR_ASIN_DD(v) pgr_cr_asin_dd(v)
-#define PGR_ASIN_DD_HI(a) ((a).h)
-#define PGR_SIN_REFLECT(x, v, a) pgr_cr_sin_near_minus_asin((x), (v), (a))
-#endif
-
 // ------------------------------------------------------------------------------------
 // device-side environment description
 // ------------------------------------------------------------------------------------
@@ -128,31 +113,21 @@ static_assert(sizeof(const EnvDev*) == kFanArgsKernargOffset && alignof(FanArgs)
 //     libm for them, which is faithful but not correctly rounded, so the oracle's ORC_MATH_CR mode (the
 //     same functions in binary128, rounded once) is what this file matches bit for bit;
 //     10*ulp(t) by integer arithmetic (exact).
-// -DPGR_STRICT uses the compiler's IEEE divide/sqrt; -DPGR_FMA additionally allows
-// contraction and a 2-ulp rsqrt (fastest, NOT within 1e-8 of the reference: experiments only).
+// -DPGR_FMA (the contracted library, PGR_ARITH=contracted) allows contraction and a 2-ulp
+// rsqrt (faster, NOT within 1e-8 of the reference: no bit-parity claim).
 // ------------------------------------------------------------------------------------
-#ifdef PGR_STRICT
-#define PGR_FAST 0
-#else
-#define PGR_FAST 1
-#endif
 
 __device__ __forceinline__ double frcp(double b)
 {
-#if PGR_FAST
     double y = __builtin_amdgcn_rcp(b);
     double e = fma(-b, y, 1.0);
     y = fma(y, e, y);
     e = fma(-b, y, 1.0);
     y = fma(y, e, y);
     return y;
-#else
-    return 1.0 / b;
-#endif
 }
 __device__ __forceinline__ double fdiv(double a, double b)
 {
-#if PGR_FAST
     // one Newton step is enough before the correction (v_rcp_f64 is good to 4.6e-8)
     double y = __builtin_amdgcn_rcp(b);
     double e = fma(-b, y, 1.0);
@@ -160,9 +135,6 @@ __device__ __forceinline__ double fdiv(double a, double b)
     double q = a * y;
     double r = fma(-q, b, a);
     return fma(r, y, q);
-#else
-    return a / b;
-#endif
 }
 // 1/b to ~2e-15 (v_rcp_f64 + one Newton step): a SEED for fdiv_y, whose correction step squares
 // the seed's error -- exactly what fdiv() itself does
@@ -182,7 +154,6 @@ __device__ __forceinline__ double fdiv_y(double a, double b, double y)
 // 1/sqrt(x), x > 0 and normal: raw Newton form (<= 2 ulp), building block of fsqrt
 __device__ __forceinline__ double frsqrt_raw(double x)
 {
-#if PGR_FAST
     double y = __builtin_amdgcn_rsq(x);
     // two Newton steps: y <- y + y*(1 - x y^2)/2
     double e = fma(-x * y, y, 1.0);
@@ -190,13 +161,9 @@ __device__ __forceinline__ double frsqrt_raw(double x)
     e = fma(-x * y, y, 1.0);
     y = fma(y * 0.5, e, y);
     return y;
-#else
-    return 1 / sqrt(x);
-#endif
 }
 __device__ __forceinline__ double fsqrt(double x)
 {
-#if PGR_FAST
     double y = __builtin_amdgcn_rsq(x);  // good to 5.2e-8: one Newton step, then the residual
     double e = fma(-x * y, y, 1.0);
     y = fma(y * 0.5, e, y);
@@ -206,9 +173,6 @@ __device__ __forceinline__ double fsqrt(double x)
     // no branch: sqrt(+-0) = +-0 and sqrt(inf) = inf by select (rsq gives inf / 0 there and the
     // refinement NaN); x < 0 and NaN come out NaN by themselves
     return (x == 0.0 || x == INFINITY) ? x : r;
-#else
-    return sqrt(x);
-#endif
 }
 // the reference's `1 / np.sqrt(arg)`: RN(1 / RN(sqrt x)).  The refined rsq is an excellent seed
 // for 1/s (s = RN(sqrt x)): one correction step lands on the correctly rounded reciprocal.
@@ -216,7 +180,7 @@ __device__ __forceinline__ double frsqrt(double x)
 {
 #ifdef PGR_FMA
     return frsqrt_raw(x);
-#elif PGR_FAST
+#else
     double y = __builtin_amdgcn_rsq(x);
     double e = fma(-x * y, y, 1.0);
     y = fma(y * 0.5, e, y);
@@ -238,38 +202,19 @@ __device__ __forceinline__ double frsqrt(double x)
     // unless 1/s lies within ~2^-96 (relative) of a rounding boundary, the same class as fdiv().
     double out = fma(y, r, y);
     return out;
-#else
-    return 1 / sqrt(x);
 #endif
 }
-// err ** -0.2 for err in [1e-7, 1e4], correctly rounded (pgr_crmath.h; -DPGR_POW_2ULP: the 2-ulp
-// Newton iteration of round 1, 18 instructions shorter -- experiments only, NOT bit-identical)
+// err ** -0.2 for err in [1e-7, 1e4], correctly rounded (pgr_crmath.h)
 __device__ __forceinline__ double pow_m02(double x, const double fifth = 0.2, const double kln2 = PGR_CR_POW_KLN2)
 {
-#ifdef PGR_POW_2ULP
-    float xf = (float)x;
-    double y = (double)__builtin_amdgcn_exp2f(-0.2f * __builtin_amdgcn_logf(xf));
-#pragma unroll
-    for (int k = 0; k < 2; k++) {
-        double y2 = y * y, y4 = y2 * y2, y5 = y4 * y;
-        double e = fma(-x, y5, 1.0);
-        y = fma(y * 0.2, e, y);
-    }
-    return y;
-#else
     return pgr_cr_pow_m02_k(x, fifth, kln2);
-#endif
 }
 // 10 * |nextafter(t, +inf) - t|, SCIPY/rk.py:119
 __device__ __forceinline__ double min_step_of(double t)
 {
-#if PGR_FAST
     long long b = __double_as_longlong(t);
     double nx = (t == 0.0) ? 4.9406564584124654e-324 : __longlong_as_double(t > 0 ? b + 1 : b - 1);
     return 10 * fabs(nx - t);
-#else
-    return 10 * fabs(nextafter(t, INFINITY) - t);
-#endif
 }
 // g0 + j*dg with NO contraction: must reproduce the table coordinate bit for bit
 __device__ __forceinline__ double grid_at(double g0, double dg, int j)
@@ -473,11 +418,7 @@ struct Ctx {
     {
         if (!(x > r_lo && x <= r_hi)) refill(x);
         i = r_i;
-#if PGR_FAST
         return fdiv_y(x - r_lo, r_hi - r_lo, r_yden);
-#else
-        return (x - r_lo) / (r_hi - r_lo);
-#endif
     }
 
     // bilinear c and dc/dz at (x, z): REF/integration_processes.py:101-174, both tables at once
@@ -574,20 +515,8 @@ struct Ctx {
             // generic pointer: flat_load + a wait on both counters; it IS global memory)
             typedef double __attribute__((ext_vector_type(2))) d2v;
             typedef const d2v __attribute__((address_space(1))) * GlobalTab;
-#ifdef PGR_CELL_RECORDS
-            // (experiment, round 6: the four corner nodes of cell (i, j) as ONE 64-byte record -- one line per look-up instead
-            // of two pieces of two rows nz x 16 B apart; 4 x the table.  Measured, not kept: LABNOTES round 6)
-            const GlobalTab row = (GlobalTab)h_tab + ((size_t)i * (size_t)(h_nz - 1) + (size_t)j) * 4;
-            const d2v t00 = row[0], t01 = row[1], t10 = row[2], t11 = row[3];
-#elif defined(PGR_ROW_PAIRS)
-            // (experiment, round 6: rows i and i + 1 interleaved node by node, [nr - 1][nz][2]: the four corner nodes are 64
-            // contiguous bytes as with the cell records, for 2 x the table instead of 4 x.  Measured: LABNOTES round 6)
-            const GlobalTab row = (GlobalTab)h_tab + ((size_t)i * (size_t)h_nz + (size_t)j) * 2;
-            const d2v t00 = row[0], t10 = row[1], t01 = row[2], t11 = row[3];
-#else
             const GlobalTab row = (GlobalTab)h_tab + (size_t)i * h_row_stride + j;
             const d2v t00 = row[0], t01 = row[1], t10 = row[h_row_stride], t11 = row[h_row_stride + 1];
-#endif
             f.v00 = make_double2(t00.x, t00.y);
             f.v01 = make_double2(t01.x, t01.y);
             f.v10 = make_double2(t10.x, t10.y);
@@ -670,26 +599,15 @@ struct Ctx {
         double cp;
         blend(ft, wx, c, cp);
         double arg = 1.0 - (c * c) * (pz * pz);
-#if PGR_FAST
         // `if arg <= 0: arg = 1e-30` as one v_max_f64: 1 - x is 0, negative or >= 2^-53, never in
         // (0, 1e-30).  (A NaN arg -- c or pz NaN -- becomes 1e-30 here; d1 and d2 are NaN through
         // their own factors all the same, and the error norm with them.)
         arg = fmax(arg, k_tiny);
-#else
-        if (arg <= 0.0) arg = 1e-30;
-#endif
-#if PGR_FAST
         double fact = frsqrt(arg);
         double rc = frcp_seed(c);  // seeds both quotients below (1/c and, squared, 1/c^2)
         d0 = fdiv_y(fact, c, rc);
         d1 = c * pz * fact;
         d2 = fdiv_y(-fact * cp, c * c, rc * rc);
-#else
-        double fact = 1 / sqrt(arg);
-        d0 = fact / c;
-        d1 = c * pz * fact;
-        d2 = -fact * cp / (c * c);
-#endif
     }
 
     // Range weights (and cells) of the five stage abscissae x_s = t + C_s h of ONE step attempt,
@@ -707,11 +625,7 @@ struct Ctx {
             const double den = r_hi - r_lo;
 #pragma unroll
             for (int s = 0; s < 5; s++) {
-#if PGR_FAST
                 w[s] = fdiv_y(xs[s] - r_lo, den, r_yden);
-#else
-                w[s] = (xs[s] - r_lo) / den;
-#endif
                 ic[s] = r_i;
             }
         } else {
@@ -728,11 +642,7 @@ struct Ctx {
                 for (int s = 0; s < 5; s++) {
                     const bool in_b = xs[s] > r_hi;
                     const double lo = in_b ? r_hi : r_lo, den = in_b ? b_den : a_den, yd = in_b ? b_yden : r_yden;
-#if PGR_FAST
                     w[s] = fdiv_y(xs[s] - lo, den, yd);
-#else
-                    w[s] = (xs[s] - lo) / den;
-#endif
                     ic[s] = r_i + (in_b ? 1 : 0);
                 }
             } else {
@@ -777,12 +687,8 @@ __device__ __forceinline__ double rms3(double a, double b, double c, double sqrt
                                        double inv_sqrt3 = 0.57735026918962584)
 {
     // np.linalg.norm(x) / x.size ** 0.5, SCIPY/common.py:63-65
-#if PGR_FAST
     // x / 3**0.5 with the (correctly rounded) reciprocal of the constant as Markstein seed
     return fdiv_y(fsqrt(a * a + b * b + c * c), sqrt3, inv_sqrt3);
-#else
-    return sqrt(a * a + b * b + c * c) / 1.7320508075688772;
-#endif
 }
 
 // quartic dense output of one accepted step: Q = K.T @ P (SCIPY/rk.py:178-180, 393-404)

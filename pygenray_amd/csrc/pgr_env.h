@@ -281,27 +281,6 @@ extern "C" int pgr_env_create(pgr_env** out, int device, const double* cin, cons
     }
     EnvDev& d = e->d;
     int rc = 0;
-#ifdef PGR_CELL_RECORDS
-    if (!indep) {   // (experiment: {c, cp} of (i, j), (i, j + 1), (i + 1, j), (i + 1, j + 1) per cell, see Ctx::fetch_nodes)
-        std::vector<double2> rec((size_t)(nr - 1) * (size_t)(nz - 1) * 4);
-        for (int64_t i = 0; i + 1 < nr; i++)
-            for (int64_t j = 0; j + 1 < nz; j++) {
-                double2* q = &rec[((size_t)i * (size_t)(nz - 1) + (size_t)j) * 4];
-                q[0] = tab[i * nz + j]; q[1] = tab[i * nz + j + 1]; q[2] = tab[(i + 1) * nz + j]; q[3] = tab[(i + 1) * nz + j + 1];
-            }
-        tab.swap(rec);
-    }
-#elif defined(PGR_ROW_PAIRS)
-    if (!indep) {   // (experiment: {c, cp} of (i, j) and (i + 1, j) side by side, see Ctx::fetch_nodes)
-        std::vector<double2> rec((size_t)(nr - 1) * (size_t)nz * 2);
-        for (int64_t i = 0; i + 1 < nr; i++)
-            for (int64_t j = 0; j < nz; j++) {
-                rec[((size_t)i * (size_t)nz + (size_t)j) * 2] = tab[i * nz + j];
-                rec[((size_t)i * (size_t)nz + (size_t)j) * 2 + 1] = tab[(i + 1) * nz + j];
-            }
-        tab.swap(rec);
-    }
-#endif
     rc |= upload(e, tab.data(), tab.size(), &d.tab);
     rc |= upload(e, rin, (size_t)nr, &d.rin);
     rc |= upload(e, zin, (size_t)nz, &d.zin);

@@ -248,35 +248,31 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, FanArgs a)
     PGR_VCONST(E7);
 #undef PGR_VCONST
     // ... and, in the kernels that save trajectories, the 18 coefficients of the stage-major sample form
-#ifndef PGR_PIN_P   // (not where the depth search already fills the register file: those instances spill otherwise)
-#define PGR_PIN_P (SAVE != 0 && ZM != 0 && ZM != 3)
-#endif
+    constexpr bool PIN_P = (SAVE != 0 && ZM != 0 && ZM != 3);  // (not where the depth search already fills the register file: those instances spill otherwise)
 #define PGR_VCONST_IF(c, n) double v##n = n; if (c) asm volatile("" : "+v"(v##n))
-    PGR_VCONST_IF(PGR_PIN_P, P11);
-    PGR_VCONST_IF(PGR_PIN_P, P12);
-    PGR_VCONST_IF(PGR_PIN_P, P13);
-    PGR_VCONST_IF(PGR_PIN_P, P31);
-    PGR_VCONST_IF(PGR_PIN_P, P32);
-    PGR_VCONST_IF(PGR_PIN_P, P33);
-    PGR_VCONST_IF(PGR_PIN_P, P41);
-    PGR_VCONST_IF(PGR_PIN_P, P42);
-    PGR_VCONST_IF(PGR_PIN_P, P43);
-    PGR_VCONST_IF(PGR_PIN_P, P51);
-    PGR_VCONST_IF(PGR_PIN_P, P52);
-    PGR_VCONST_IF(PGR_PIN_P, P53);
-    PGR_VCONST_IF(PGR_PIN_P, P61);
-    PGR_VCONST_IF(PGR_PIN_P, P62);
-    PGR_VCONST_IF(PGR_PIN_P, P63);
-    PGR_VCONST_IF(PGR_PIN_P, P71);
-    PGR_VCONST_IF(PGR_PIN_P, P72);
-    PGR_VCONST_IF(PGR_PIN_P, P73);
+    PGR_VCONST_IF(PIN_P, P11);
+    PGR_VCONST_IF(PIN_P, P12);
+    PGR_VCONST_IF(PIN_P, P13);
+    PGR_VCONST_IF(PIN_P, P31);
+    PGR_VCONST_IF(PIN_P, P32);
+    PGR_VCONST_IF(PIN_P, P33);
+    PGR_VCONST_IF(PIN_P, P41);
+    PGR_VCONST_IF(PIN_P, P42);
+    PGR_VCONST_IF(PIN_P, P43);
+    PGR_VCONST_IF(PIN_P, P51);
+    PGR_VCONST_IF(PIN_P, P52);
+    PGR_VCONST_IF(PIN_P, P53);
+    PGR_VCONST_IF(PIN_P, P61);
+    PGR_VCONST_IF(PIN_P, P62);
+    PGR_VCONST_IF(PIN_P, P63);
+    PGR_VCONST_IF(PIN_P, P71);
+    PGR_VCONST_IF(PIN_P, P72);
+    PGR_VCONST_IF(PIN_P, P73);
 #undef PGR_VCONST_IF
     // ... and the remaining fp64 literals of a step attempt (stage abscissae, controller and norm
     // constants, the RHS clamp): 26 s_mov_b32 per attempt otherwise
-#ifndef PGR_PIN_LITERALS
-#define PGR_PIN_LITERALS (SAVE == 0 || ZM == 3)
-#endif
-    if (PGR_PIN_LITERALS) {
+    constexpr bool PIN_LITERALS = (SAVE == 0 || ZM == 3);
+    if (PIN_LITERALS) {
 #define PGR_PIN(x) asm volatile("" : "+v"(x))
         PGR_PIN(C.k_c2); PGR_PIN(C.k_c3); PGR_PIN(C.k_c4); PGR_PIN(C.k_c5); PGR_PIN(C.k_tiny); PGR_PIN(C.k_vert);
         PGR_PIN(SAFETY); PGR_PIN(MIN_FACTOR); PGR_PIN(MAX_FACTOR);
@@ -287,14 +283,12 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, FanArgs a)
     // ZM == 5: a Horner step whose multiplier AND addend are wave-uniform costs a v_mov (one scalar operand per
     // VALU instruction): the addend of the first step of the index cubic and of the seed quadratic sit in VGPRs
     // (6 look-ups per attempt use them)
-#ifndef PGR_PIN_ZC   // (A/B, flat-earth fan: all seven in VGPRs 6.86 vs 7.02 ms with trajectories, 5.78 vs 5.75 ms without)
-#define PGR_PIN_ZC (SAVE != 0 ? 2 : 1)
-#endif
-    if (ZM == 5 && (PGR_PIN_ZC) >= 1) {
+    constexpr int PIN_ZC = (SAVE != 0 ? 2 : 1);  // (A/B, flat-earth fan: all seven in VGPRs 6.86 vs 7.02 ms with trajectories, 5.78 vs 5.75 ms without)
+    if (ZM == 5 && PIN_ZC >= 1) {
         asm volatile("" : "+v"(C.h_zc_g2));
         asm volatile("" : "+v"(C.h_zc_s1));
     }
-    if (ZM == 5 && (PGR_PIN_ZC) >= 2) {   // all seven: the scalar file of the trajectory kernels is full of loop values already
+    if (ZM == 5 && PIN_ZC >= 2) {   // all seven: the scalar file of the trajectory kernels is full of loop values already
         asm volatile("" : "+v"(C.h_zc_g0));
         asm volatile("" : "+v"(C.h_zc_g1));
         asm volatile("" : "+v"(C.h_zc_g3));
@@ -307,10 +301,7 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, FanArgs a)
     // instructions shorter).  Costs no register: the values are live to the end of an attempt anyway, and the early
     // stages of the next one have room (same VGPR count, same spill count, four v_readlane fewer in the step loop) -- except
     // in the ZM = 5 trajectory instances, whose look-up coefficients fill the file (12 -> 28 spills): those keep the replay.
-#ifndef PGR_KEEP_K
-#define PGR_KEEP_K (!(ZM == 5 && SAVE != 0))
-#endif
-    constexpr bool KEEPK = PGR_KEEP_K;
+    constexpr bool KEEPK = !(ZM == 5 && SAVE != 0);
     double k30 = 0, k31 = 0, k32 = 0, k40 = 0, k41 = 0, k42 = 0, k50 = 0, k51 = 0, k52 = 0, k60 = 0, k61 = 0, k62 = 0,
            k70 = 0, k71 = 0, k72 = 0;
     // One trip = one step attempt of every stepping lane, THEN the gate that decides whether the
@@ -614,7 +605,6 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, FanArgs a)
                             // that the surface root is the earlier one (SCIPY/ivp.py:100-131)
                             live = (xa < xb) && !ga && gb && !(with_bbox && bbox_b);
                             PGR_SSTAMP(4);    // band + the true event at its two edges
-#ifndef PGR_NO_BAND_TABLE
                             // The doubles strictly inside the band: one or two once the noise band is narrower than
                             // an ulp of x (beyond ~100 km).  Evaluate the true event there as well, and if it flips
                             // once the band shrinks to the flip itself, (last double not fired, first double fired):
@@ -636,12 +626,8 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, FanArgs a)
                                     xa = nxa;
                                 }
                             }
-#endif
                             PGR_SSTAMP(5);    // the doubles inside a narrow band
                         }
-#ifdef PGR_NO_REPLAY  // experiments: round 1's "a root within brentq's tolerance" (NOT bit-identical)
-                        if (live) { best = xb; ev = bottom ? 1 : 0; }
-#else
                         // ---- the replay.  brentq's state: cur = the latest iterate, xblk = the other end of
                         // the bracket, fcur = the event at cur; it starts from cur = t_new (fired), xblk = t.
                         const double xtol = 4 * DBL_EPSILON, brtol = 4 * DBL_EPSILON;
@@ -705,7 +691,6 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, FanArgs a)
                         }
                         if (live && done) { best = cur; ev = bottom ? 1 : 0; }
                         PGR_SSTAMP(7);    // replay phase 2
-#endif
                     }
                     if (ev < 0) {
                         fallbacks++;
@@ -766,8 +751,8 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, FanArgs a)
                             double c, cp;
                             C.lookup(t, y1, c, cp);
                             const double pc_b = y2 * c;
-                            const PGR_ASIN_DD_T A_b = PGR_ASIN_DD(pc_b);
-                            double theta = PGR_ASIN_DD_HI(A_b) * (180.0 / M_PI);  // ray_angle
+                            const struct pgr_dd A_b = pgr_cr_asin_dd(pc_b);
+                            double theta = A_b.h * (180.0 / M_PI);  // ray_angle
                             double theta_b;
                             PGR_SSTAMP(11);   // look-up + arcsine
                             if (ev == 0) {
@@ -805,7 +790,7 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, FanArgs a)
                                     status = PGR_RAY_BACKWARD;
                                 else {
                                     // (theta_b = -theta at the surface and on a flat floor: the sine of minus an arcsine, cheaply)
-                                    y2 = fdiv(PGR_SIN_REFLECT(theta_b * (M_PI / 180.0), pc_b, A_b), c);
+                                    y2 = fdiv(pgr_cr_sin_near_minus_asin(theta_b * (M_PI / 180.0), pc_b, A_b), c);
                                     need_init = true;
                                     if (!(t < t_bound)) status = PGR_RAY_OK;
                                     else if (n_steps > max_steps32) status = PGR_RAY_MAX_STEPS;

@@ -103,21 +103,10 @@ extern "C" const char* pgr_build_info(void)
         std::string t(pgr_build_tag + 14);
         while (!t.empty() && t.back() == ' ') t.pop_back();
         info = "layout: " + t + "; arithmetic: ";
-#if defined(PGR_FMA)
+#ifdef PGR_FMA
         info += "FMA contraction allowed (the PGR_ARITH=contracted opt-in: NOT the reference's bits, no bit-parity claim)";
-#elif defined(PGR_STRICT)
-        info += "compiler IEEE divide/sqrt";
 #else
         info += "reference order, correctly rounded div/sqrt/pow/asin/sin";
-#endif
-#ifdef PGR_POW_2ULP
-        info += ", 2-ulp pow (NOT bit-identical)";
-#endif
-#ifdef PGR_NO_REPLAY
-        info += ", no brentq replay (NOT bit-identical)";
-#endif
-#ifdef PGR_LIBM_TRIG
-        info += ", device-library asin/sin (NOT bit-identical)";
 #endif
     });
     return info.c_str();
