@@ -245,6 +245,30 @@ int pgr_arrival_histogram_device(int device, const double* t_end, int64_t t_stri
                                  double t_min, double t_max, int32_t nbins, int64_t* counts,
                                  void* stream);
 
+/* Ray-tube intensity of a fan on a range-depth grid (the transmission loss of DESIGN.md, "Transmission loss"): adjacent
+ * surviving rays k, k + 1 (launch order) bound a tube; at save sample s, with g = c / sqrt(1 - (p c)^2) and c the bilinear
+ * sound speed of the environment the fan was traced in,
+ *   I_k(s) = 0.5 (g_k + g_k+1) |p0_k+1 - p0_k| / (r_s |z_k+1 - z_k|),   r_s = |x_s - x_0|,
+ * and out[j * S + s] (DEVICE, [n_depths][S], overwritten) = the sum, in increasing k starting from 0.0, of I_k(s) over the
+ * tubes whose depth interval [min, max) of their two samples holds depths[j].  A tube with a NaN sample, |p c| >= 1 at
+ * either end or z_k+1 == z_k adds nothing (a receiver no tube reaches gets 0); the column r_s == 0 is NaN.  Depths are
+ * positive down.  Deterministic: no atomics, every receiver's sum is formed in tube order by one lane, so repeated calls
+ * are bit-equal and equal the sequential sum.  TL = -10 log10(out).
+ *
+ * pgr_fan_intensity: a device-resident fan (either trajectory layout it holds; dropped rays are skipped in place, nothing
+ * is copied or fetched).  Waits for the fan's kernel, then enqueues on `stream` and returns without synchronising.
+ * p0[M] (DEVICE): the launch slowness of the M surviving rays in launch order (only |p0_k+1 - p0_k| enters); depths[n_depths]
+ * (DEVICE).  Needs M >= 2 and a fan launched with trajectories.  Sample depths are read as launched (PGR_STORED_SIGN:
+ * depth = -z). */
+int pgr_fan_intensity(pgr_fan* fan, const double* p0, const double* depths, int64_t n_depths, double* out, void* stream);
+
+/* The same for caller buffers: z, p (DEVICE) [n_samples][n_rays] rows, stored sign convention (depth = -z, as RayFan.zs),
+ * every ray a tube edge; x[n_samples] (DEVICE) the save ranges in the frame of `env` (mirrored, x -> -x, for a backwards fan);
+ * p0[n_rays], depths[n_depths], out[n_depths][n_samples] as above.  Enqueued on `stream`, returns without synchronising. */
+int pgr_intensity_device(pgr_env* env, const double* z, const double* p, int64_t n_rays, int32_t n_samples,
+                         const double* x, const double* p0, const double* depths, int64_t n_depths, double* out,
+                         void* stream);
+
 /* Tuning options of ONE environment (per-ray results never depend on them; there is no process-wide
  * state: host threads that drive different GPUs hold different environments).
  *   PGR_OPT_WAVES_PER_BLOCK  a = waves (of 64 rays) per workgroup, 0 = automatic

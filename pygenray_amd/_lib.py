@@ -514,6 +514,14 @@ class FanHandle:
         return {k: (v.reshape(-1)[:self.S * cols].reshape(self.S, cols) if cols != self.N else v)
                 for k, v in bufs.items() if v is not None}
 
+    def intensity(self, p0_ptr, depths_ptr, n_depths, out_ptr, stream=0):
+        """pgr_fan_intensity on raw device pointers (ints): out[n_depths][S] = the ray-tube intensity of this fan's surviving
+        rays at the receiver depths (include/pgr.h); p0 holds the M surviving rays' launch slowness.  Enqueued on `stream`."""
+        L = load()
+        L.pgr_fan_intensity.restype = ctypes.c_int
+        L.pgr_fan_intensity.argtypes = [_vp, _vp, _vp, _i64, _vp, _vp]
+        check(L.pgr_fan_intensity(self._h, _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vp(out_ptr), _vp(stream or None)))
+
     def close(self):
         if getattr(self, "_h", None):
             load().pgr_fan_destroy(self._h)
@@ -601,3 +609,13 @@ def arrival_histogram_device(device, t_ptr, t_stride, status_ptr, status_stride,
     check(L.pgr_arrival_histogram_device(int(device), _vp(t_ptr), int(t_stride), _vp(status_ptr or None),
                                          int(status_stride), int(n), float(t_min), float(t_max), int(nbins),
                                          _vp(counts_ptr), _vp(stream or None)))
+
+
+def intensity_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, depths_ptr, n_depths, out_ptr, stream=0):
+    """pgr_intensity_device on raw device pointers (ints): the ray-tube intensity of caller buffers z / p [n_samples][n_rays]
+    (stored sign convention) on `env` (an EnvHandle); see include/pgr.h."""
+    L = load()
+    L.pgr_intensity_device.restype = ctypes.c_int
+    L.pgr_intensity_device.argtypes = [_vp, _vp, _vp, _i64, ctypes.c_int32, _vp, _vp, _vp, _i64, _vp, _vp]
+    check(L.pgr_intensity_device(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples), _vp(x_ptr), _vp(p0_ptr),
+                                 _vp(depths_ptr), int(n_depths), _vp(out_ptr), _vp(stream or None)))

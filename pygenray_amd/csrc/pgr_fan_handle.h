@@ -51,6 +51,7 @@ struct pgr_fan {
     pgr_env* env = nullptr;
     int64_t N = 0, M = -1;
     int32_t S = 0;
+    double x0 = 0.0, x1 = 0.0;   // source / receiver range of the launch (the kernel forms the save ranges from them, `r` is not written)
     uint32_t flags = 0;
     bool save = false, finished = false;
     bool blocked = false;   // T / Z / P are held sample-blocked, [ceil(S/4)][N][4] (PGR_SAMPLE_BLOCKED): every fetch un-blocks
@@ -67,6 +68,8 @@ struct pgr_fan {
     // for the whole device, i.e. for other fans in flight on other streams)
     void* scratch = nullptr;
     size_t scratch_bytes = 0;
+    int* d_keep = nullptr;  // the surviving rays' columns on the device (pgr_fan_intensity, pgr_tl.h): uploaded once, freed with the handle
+    bool r_filled = false;  // `r` holds the save ranges (pgr_fan_intensity fills it on first use)
     std::mutex m;
 };
 
@@ -77,6 +80,7 @@ extern "C" void pgr_fan_destroy(pgr_fan* f)
     (void)hipSetDevice(env->device);
     if (f->done) { (void)hipEventSynchronize(f->done); (void)hipEventDestroy(f->done); }
     if (f->scratch) (void)hipFree(f->scratch);
+    if (f->d_keep) (void)hipFree(f->d_keep);
     bool last = false;
     {
         std::lock_guard<std::mutex> lock(env->fan_pool_mutex);
@@ -110,6 +114,7 @@ extern "C" int pgr_fan_launch(pgr_env* env, const double* y0, const double* ode_
     }
     pgr_fan* f = new pgr_fan();
     f->env = env; f->N = N; f->S = S; f->save = (S > 0);
+    f->x0 = source_range; f->x1 = receiver_range;
     {
         std::lock_guard<std::mutex> lock(env->fan_pool_mutex);
         env->live_fans++;

@@ -52,3 +52,4 @@
 #include "pgr_fan_handle.h"     // pgr_initial_states_device, pgr_fan_*
 #include "pgr_eigen_hist.h"     // pgr_eigen_refine*, pgr_arrival_histogram_device
 #include "pgr_debug_entry.h"    // pgr_debug_math / pgr_debug_step / pgr_eval_points
+#include "pgr_tl.h"             // ray-tube intensity / transmission loss: pgr_fan_intensity, pgr_intensity_device
