@@ -1,5 +1,8 @@
 """transmission_loss without a GPU: the ray-tube definition itself (its NumPy restatement in tests/tl_reference.py) against
-the isovelocity image-source sum, and the argument errors refused before anything reaches the device."""
+the isovelocity image-source sum and against the closed form of a linear sound-speed gradient (a CPU-oracle fan), and the
+argument errors refused before anything reaches the device."""
+import math
+
 import numpy as np
 import pytest
 
@@ -89,3 +92,52 @@ def test_flatearth_without_the_transform_is_refused_with_the_reference_message()
 
 def test_transmission_loss_is_exported():
     assert "transmission_loss" in pr.__all__ and callable(pr.transmission_loss)
+
+
+# ---- a refracting medium: c = 1520 - 0.02 z, rays are circular arcs (tl_reference.linear_gradient_intensity) ------------
+
+CA, GAMMA, ZS_G, AP = tlr.GRADIENT_CA, tlr.GRADIENT_GAMMA, tlr.GRADIENT_ZS, tlr.GRADIENT_APERTURE
+
+
+def _oracle_gradient_fan():
+    import oracle
+    from helpers import y0_for
+    env = tlr.gradient_env()
+    arrs = pr._unpack_envi(env, flatearth=False)
+    theta = np.linspace(-AP, AP, 2001)                                # depth-down (ODE convention)
+    y0 = y0_for(oracle, arrs, ZS_G, 0.0, theta)
+    o = oracle.shoot_fan(*arrs, y0, 0.0, tlr.GRADIENT_X1, tlr.GRADIENT_S)
+    assert (o["status"] == 0).all()
+    cin, _, rin, zin = arrs[:4]
+    I = tlr.tube_intensity(-o["z"], -o["p"], o["r"], y0[:, 2], tlr.GRADIENT_DEPTHS, cin, rin, zin)
+    return o, np.radians(theta), I
+
+
+def test_closed_form_derivative_matches_mpmath():
+    import mpmath
+    mpmath.mp.dps = 40
+    for r in (1e3, 7.5e3, 15e3):
+        for t in np.radians([-8.0, -3.3, 0.0, 2.1, 8.0]):
+            _, _, dz = tlr.linear_gradient_ray(r, float(t), ZS_G, CA, GAMMA, m=math)
+            num = mpmath.diff(lambda u: tlr.linear_gradient_ray(r, u, ZS_G, CA, GAMMA, m=mpmath)[0], mpmath.mpf(float(t)))
+            assert abs(dz - float(num)) <= 1e-9 * abs(float(num)), (r, t, dz, num)
+    # and the isovelocity limit: I -> 1 / R^2
+    I = tlr.linear_gradient_intensity([5e3], [1500.0], ZS_G, 1500.0, 1e-9, -8.0, 8.0)
+    assert abs(I[0, 0] * (5e3 ** 2 + 500.0 ** 2) - 1) < 1e-6
+
+
+def test_restatement_matches_the_linear_gradient_closed_form():
+    o, theta0, I = _oracle_gradient_fan()
+    worst, ref, inside = tlr.check_gradient_fan(o["r"], -o["z"], I, theta0, o["n_bott"], o["n_surf"])
+    # measured: 1.49e-4 dB worst (median 1.8e-5) over 12 817 receivers inside the wedge
+    assert worst < 2e-4
+    # the test's power: the definition with c_s for c(d), or with cos(theta0) for cos(theta(r)), misses the bound >= 10x
+    x = o["r"][o["r"] >= 1e3]
+    c_s = CA + GAMMA * ZS_G
+    _, th = tlr.linear_gradient_intensity(x, tlr.GRADIENT_DEPTHS, ZS_G, CA, GAMMA, -AP, AP, _solve=True)
+    th = np.where(inside, th, 0.0)
+    k_r = tlr.linear_gradient_ray(x[None, :], th, ZS_G, CA, GAMMA)[1]
+    Ik = I[:, o["r"] >= 1e3][inside]
+    for wrong in (ref * c_s / (CA + GAMMA * tlr.GRADIENT_DEPTHS[:, None]), ref * k_r / np.cos(th)):
+        miss = np.abs(tlr.to_db(Ik) - tlr.to_db(wrong[inside])).max()
+        assert miss > 10 * tlr.TOL_DB_GRADIENT, miss
