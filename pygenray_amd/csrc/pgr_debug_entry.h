@@ -6,10 +6,8 @@
 extern "C" int pgr_debug_math(const double* a, const double* b, int64_t M, double* out9)
 {
     if (!a || !b || !out9 || M <= 0) return fail("pgr_debug_math: bad argument");
-    struct Buf { void* p = nullptr; ~Buf() { if (p) (void)hipFree(p); } } da, db, dout;
-    HIPCHK(hipMalloc(&da.p, M * 8));
-    HIPCHK(hipMalloc(&db.p, M * 8));
-    HIPCHK(hipMalloc(&dout.p, M * 72));
+    DevBuf da, db, dout;
+    if (da.alloc(M * 8) || db.alloc(M * 8) || dout.alloc(M * 72)) return fail("device allocation failed");
     HIPCHK(hipMemcpy(da.p, a, M * 8, hipMemcpyHostToDevice));
     HIPCHK(hipMemcpy(db.p, b, M * 8, hipMemcpyHostToDevice));
     hipLaunchKernelGGL(pgr_math_kernel, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, 0,

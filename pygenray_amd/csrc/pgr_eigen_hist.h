@@ -137,8 +137,8 @@ extern "C" int pgr_eigen_refine_depths_fn(pgr_env* env, int64_t nbk, const doubl
         return fail("pgr_eigen_refine: null argument");
     if (!(c_source > 0) || !(ztol > 0) || max_iter < 0) return fail("pgr_eigen_refine: bad argument");
     HIPCHK(hipSetDevice(env->device));
+    if (env_stream(env)) return -1;
     std::lock_guard<std::mutex> lock(env->ws_mutex);
-    if (!env->stream) HIPCHK(hipStreamCreateWithFlags(&env->stream, hipStreamNonBlocking));
     hipStream_t st = env->stream;
     // The trial rays of different brackets have nothing in common -- launch angles anywhere in the fan, bounces at
     // different ranges: 64 of them in one wave make that wave service bounces all the time (a service costs the whole
@@ -148,35 +148,29 @@ extern "C" int pgr_eigen_refine_depths_fn(pgr_env* env, int64_t nbk, const doubl
     int64_t per_wave = 1;
     while (per_wave < 64 && (nbk + per_wave - 1) / per_wave > 1024) per_wave *= 2;
     const int64_t spread = 64 / per_wave;
-    // one device block: 4 bracket arrays, theta, z_end, t_end [nbk] (doubles), y0[3], end[3] [nbk * spread], 3 int arrays
-    // [nbk * spread], 2 [nbk], the counter
+    // one device block (Carve): 4 bracket arrays, theta, z_end, t_end, receiver depths [nbk]; y0, end [nbk * spread][3];
+    // status, n_bott, n_surf [nbk * spread]; state, n_trial [nbk]; the counter; p0 [nbk] (callback mode only)
     const size_t nd = (size_t)nbk, nr = (size_t)(nbk * spread);
-    const size_t bytes = nd * 8 * 8 + nr * 8 * 6 + nr * 4 * 3 + nd * 4 * 2 + 256 + (slowness ? nd * 8 + 256 : 0);
-    // (the environment's grow-only workspace -- the host-pointer fan entry's, which this call does not use: the
-    // many small searches of a receiver-depth loop pay no allocation)
-    if (bytes > env->ws_bytes) {
-        if (env->ws) (void)hipFree(env->ws);
-        env->ws = nullptr; env->ws_bytes = 0;
-        const size_t want = bytes > ((size_t)1 << 20) ? bytes : ((size_t)1 << 20);
-        if (hipMalloc(&env->ws, want) != hipSuccess) { env->ws = nullptr; return fail("pgr_eigen_refine: device allocation failed"); }
-        env->ws_bytes = want;
-    }
-    double* d = (double*)env->ws;
     EigenState e{};
     e.spread = spread;
-    e.th1 = d; e.th2 = d + nd; e.z1 = d + 2 * nd; e.z2 = d + 3 * nd; e.theta = d + 4 * nd;
-    e.z_end = d + 5 * nd; e.t_end = d + 6 * nd;
-    double* d_rd = d + 7 * nd;
-    e.rd = d_rd;
-    e.y0 = d + 8 * nd;
-    double* end = d + 8 * nd + 3 * nr;
-    e.end = end;
-    int32_t* ib = (int32_t*)(d + 8 * nd + 6 * nr);
-    int32_t* status = ib; e.status = status;
-    int32_t* nbott = ib + nr; int32_t* nsurf = ib + 2 * nr;
-    e.state = ib + 3 * nr; e.n_trial = ib + 3 * nr + nd;
-    e.n_active = ib + 3 * nr + 2 * nd;
-    double* d_p0 = (double*)(((uintptr_t)(e.n_active + 1) + 255) & ~(uintptr_t)255);   // (callback mode only; inside `bytes`)
+    double *d_rd, *end, *d_p0;
+    int32_t *status, *nbott, *nsurf;
+    auto carve = [&](void* base) {
+        Carve c{(char*)base};
+        e.th1 = c.take<double>(nd); e.th2 = c.take<double>(nd); e.z1 = c.take<double>(nd); e.z2 = c.take<double>(nd);
+        e.theta = c.take<double>(nd); e.z_end = c.take<double>(nd); e.t_end = c.take<double>(nd); e.rd = d_rd = c.take<double>(nd);
+        e.y0 = c.take<double>(3 * nr); e.end = end = c.take<double>(3 * nr);
+        e.status = status = c.take<int32_t>(nr); nbott = c.take<int32_t>(nr); nsurf = c.take<int32_t>(nr);
+        e.state = c.take<int32_t>(nd); e.n_trial = c.take<int32_t>(nd); e.n_active = c.take<int32_t>(1);
+        d_p0 = c.take<double>(slowness ? nd : 0);
+        return c.total;
+    };
+    const size_t bytes = carve(nullptr);
+    // (the environment's grow-only workspace -- the host-pointer fan entry's, which this call does not use: the
+    // many small searches of a receiver-depth loop pay no allocation)
+    if (bytes > env->ws_bytes && !grow_buffer(env->ws, env->ws_bytes, bytes > ((size_t)1 << 20) ? bytes : ((size_t)1 << 20)))
+        return fail("pgr_eigen_refine: device allocation failed");
+    carve(env->ws);
     std::vector<double> h_ang, h_p0;
     std::vector<int32_t> h_state;
     if (slowness) { h_ang.resize(nd); h_p0.resize(nd); h_state.resize(nd); }

@@ -57,8 +57,7 @@ struct pgr_fan {
     bool blocked = false;   // T / Z / P are held sample-blocked, [ceil(S/4)][N][4] (PGR_SAMPLE_BLOCKED): every fetch un-blocks
     void* buf = nullptr;
     size_t buf_bytes = 0;
-    double *y0 = nullptr, *r = nullptr, *T = nullptr, *Z = nullptr, *P = nullptr, *end = nullptr;
-    int32_t *nb = nullptr, *ns = nullptr, *st = nullptr, *n1 = nullptr, *n2 = nullptr;
+    FanBufs d{};   // carved out of `buf` (fan_carve)
     hipStream_t stream = nullptr;
     hipEvent_t done = nullptr;
     std::vector<int32_t> status_host;
@@ -108,10 +107,7 @@ extern "C" int pgr_fan_launch(pgr_env* env, const double* y0, const double* ode_
     if (S < 0) return fail("pgr_fan_launch: negative num_range_save");
     if (flags & PGR_SAMPLE_BLOCKED) return fail("pgr_fan_launch: PGR_SAMPLE_BLOCKED is for pgr_shoot_fan_device (device-resident consumers)");
     HIPCHK(hipSetDevice(env->device));
-    if (!env->stream) {
-        std::lock_guard<std::mutex> lock(env->ws_mutex);
-        if (!env->stream) HIPCHK(hipStreamCreateWithFlags(&env->stream, hipStreamNonBlocking));
-    }
+    if (env_stream(env)) return -1;
     pgr_fan* f = new pgr_fan();
     f->env = env; f->N = N; f->S = S; f->save = (S > 0);
     f->x0 = source_range; f->x1 = receiver_range;
@@ -122,13 +118,9 @@ extern "C" int pgr_fan_launch(pgr_env* env, const double* y0, const double* ode_
     f->flags = (flags & ~(uint32_t)(PGR_COMPACT | PGR_PACKED_END | PGR_LAUNCH_SLOWNESS)) | PGR_SAMPLE_MAJOR | PGR_SAVE_LINSPACE;
     f->stream = env->stream;
     // environments whose tables stay in HBM / L2: the sample-blocked kernel, un-blocked when the samples are fetched
-    f->blocked = f->save && !(flags & PGR_EXACT_SAMPLES) && blocked_layout_fits(env);
+    f->blocked = fan_blocked(env, f->save, f->flags);
     if (f->blocked) f->flags |= PGR_SAMPLE_BLOCKED;
-    const size_t ns_bytes = (size_t)N * (size_t)(f->blocked ? 4 * ((S + 3) / 4) : S) * sizeof(double);
-    const size_t sizes[11] = {(size_t)N * 24, (size_t)(S > 0 ? S : 1) * 8, ns_bytes, ns_bytes, ns_bytes, (size_t)N * 24,
-                              (size_t)N * 4, (size_t)N * 4, (size_t)N * 4, (size_t)N * 4, (size_t)N * 4};
-    size_t off[11], total = 0;
-    for (int k = 0; k < 11; k++) { off[k] = total; total += (sizes[k] + 255) & ~(size_t)255; }
+    const size_t total = fan_bytes(N, S, f->save, f->blocked);
     {   // the smallest pooled buffer that fits (and is not more than twice too large), else a fresh one
         std::lock_guard<std::mutex> lock(env->fan_pool_mutex);
         int best = -1;
@@ -140,39 +132,33 @@ extern "C" int pgr_fan_launch(pgr_env* env, const double* y0, const double* ode_
             env->fan_pool.erase(env->fan_pool.begin() + best);
         }
     }
-    if (!f->buf) {
-        if (hipMalloc(&f->buf, total) != hipSuccess) { f->buf = nullptr; pgr_fan_destroy(f); return fail("pgr_fan_launch: device allocation failed"); }
-        f->buf_bytes = total;
-    }
-    char* b = (char*)f->buf;
-    f->y0 = (double*)(b + off[0]); f->r = (double*)(b + off[1]); f->T = (double*)(b + off[2]); f->Z = (double*)(b + off[3]);
-    f->P = (double*)(b + off[4]); f->end = (double*)(b + off[5]); f->nb = (int32_t*)(b + off[6]); f->ns = (int32_t*)(b + off[7]);
-    f->st = (int32_t*)(b + off[8]); f->n1 = (int32_t*)(b + off[9]); f->n2 = (int32_t*)(b + off[10]);
+    if (!grow_buffer(f->buf, f->buf_bytes, total)) { pgr_fan_destroy(f); return fail("pgr_fan_launch: device allocation failed"); }
+    f->d = fan_carve(f->buf, N, S, f->save, f->blocked);
     hipStream_t st = f->stream;
     hipEvent_t up = nullptr;
     int rc = 0;
     do {
         if (hipEventCreateWithFlags(&f->done, hipEventDisableTiming) != hipSuccess) { rc = fail("pgr_fan_launch: event"); break; }
         if (y0) {
-            if (hipMemcpyAsync(f->y0, y0, (size_t)N * 24, hipMemcpyHostToDevice, st) != hipSuccess) { rc = fail("pgr_fan_launch: upload of y0"); break; }
+            if (hipMemcpyAsync(f->d.y0, y0, (size_t)N * 24, hipMemcpyHostToDevice, st) != hipSuccess) { rc = fail("pgr_fan_launch: upload of y0"); break; }
         } else {
             // the angles ride in the (not yet used) end_state array; y0 is computed on the device
-            if (hipMemcpyAsync(f->end, ode_angles_deg, (size_t)N * 8, hipMemcpyHostToDevice, st) != hipSuccess) { rc = fail("pgr_fan_launch: upload of the angles"); break; }
+            if (hipMemcpyAsync(f->d.end, ode_angles_deg, (size_t)N * 8, hipMemcpyHostToDevice, st) != hipSuccess) { rc = fail("pgr_fan_launch: upload of the angles"); break; }
             if (flags & PGR_LAUNCH_SLOWNESS) {
                 // ... or assembled from the caller's own p0[k] = sin(radians(angle)) / c (REF/launch_rays.py:144): a third
                 // of the bytes of y0 cross PCIe and nobody builds an [N][3] array on the host
-                hipLaunchKernelGGL(pgr_y0_from_p0_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, (const double*)f->end, N,
-                                   source_depth, f->y0);
+                hipLaunchKernelGGL(pgr_y0_from_p0_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, st, (const double*)f->d.end, N,
+                                   source_depth, f->d.y0);
                 if (hipGetLastError() != hipSuccess) { rc = fail("pgr_fan_launch: y0 kernel"); break; }
             } else {
-                rc = pgr_initial_states_device(env->device, f->end, N, source_depth, c_source, f->y0, (void*)st);
+                rc = pgr_initial_states_device(env->device, f->d.end, N, source_depth, c_source, f->d.y0, (void*)st);
                 if (rc) break;
             }
         }
         if (hipEventCreateWithFlags(&up, hipEventDisableTiming) != hipSuccess || hipEventRecord(up, st) != hipSuccess) { rc = fail("pgr_fan_launch: event"); break; }
-        rc = pgr_shoot_fan_device(env, f->y0, N, source_range, receiver_range, f->r, S > 0 ? S : 1, rtol, atol, f->flags, max_steps,
-                                  f->save ? f->T : nullptr, f->save ? f->Z : nullptr, f->save ? f->P : nullptr, f->end,
-                                  f->nb, f->ns, f->st, f->n1, f->n2, (void*)st);
+        rc = pgr_shoot_fan_device(env, f->d.y0, N, source_range, receiver_range, f->d.r, S > 0 ? S : 1, rtol, atol, f->flags, max_steps,
+                                  f->save ? f->d.T : nullptr, f->save ? f->d.Z : nullptr, f->save ? f->d.P : nullptr, f->d.end,
+                                  f->d.nb, f->d.ns, f->d.st, f->d.n1, f->d.n2, (void*)st);
         if (rc) break;
         if (hipEventRecord(f->done, st) != hipSuccess) { rc = fail("pgr_fan_launch: event record"); break; }
         // the caller may release y0 / the angles when this returns: wait for the upload (not for the kernel behind it)
@@ -192,7 +178,7 @@ static int fan_finish(pgr_fan* f)
     HIPCHK(hipSetDevice(f->env->device));
     HIPCHK(hipEventSynchronize(f->done));
     f->status_host.resize((size_t)f->N);
-    HIPCHK(hipMemcpy(f->status_host.data(), f->st, (size_t)f->N * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(f->status_host.data(), f->d.st, (size_t)f->N * 4, hipMemcpyDeviceToHost));
     f->keep.clear();
     for (int64_t k = 0; k < f->N; k++) if (f->status_host[(size_t)k] == 0) f->keep.push_back((int)k);
     f->M = (int64_t)f->keep.size();
@@ -221,12 +207,12 @@ extern "C" int pgr_fan_fetch_rays(pgr_fan* f, double* end_state, int32_t* n_bott
     if (rc) return rc;
     PGR_MARK(t0, "pgr_fan_fetch_rays: kernel finished, status on the host");
     const size_t n = (size_t)f->N;
-    if (end_state) HIPCHK(hipMemcpy(end_state, f->end, n * 24, hipMemcpyDeviceToHost));
-    if (n_bott) HIPCHK(hipMemcpy(n_bott, f->nb, n * 4, hipMemcpyDeviceToHost));
-    if (n_surf) HIPCHK(hipMemcpy(n_surf, f->ns, n * 4, hipMemcpyDeviceToHost));
+    if (end_state) HIPCHK(hipMemcpy(end_state, f->d.end, n * 24, hipMemcpyDeviceToHost));
+    if (n_bott) HIPCHK(hipMemcpy(n_bott, f->d.nb, n * 4, hipMemcpyDeviceToHost));
+    if (n_surf) HIPCHK(hipMemcpy(n_surf, f->d.ns, n * 4, hipMemcpyDeviceToHost));
     if (status) memcpy(status, f->status_host.data(), n * 4);
-    if (n_steps) HIPCHK(hipMemcpy(n_steps, f->n1, n * 4, hipMemcpyDeviceToHost));
-    if (n_rej) HIPCHK(hipMemcpy(n_rej, f->n2, n * 4, hipMemcpyDeviceToHost));
+    if (n_steps) HIPCHK(hipMemcpy(n_steps, f->d.n1, n * 4, hipMemcpyDeviceToHost));
+    if (n_rej) HIPCHK(hipMemcpy(n_rej, f->d.n2, n * 4, hipMemcpyDeviceToHost));
     PGR_MARK(t0, "pgr_fan_fetch_rays: done");
     return 0;
 }
@@ -245,20 +231,15 @@ extern "C" int pgr_fan_fetch_rays_compact(pgr_fan* f, const double* per_ray_in, 
     const size_t n = (size_t)f->N, M = (size_t)f->M;
     const size_t need = n * 32;     // end[N][3] doubles, n_bott[N], n_surf[N] int32
     std::lock_guard<std::mutex> wlock(env->ws_mutex);
-    if (need > env->stage_bytes) {
-        if (env->stage) (void)hipHostFree(env->stage);
-        env->stage = nullptr; env->stage_bytes = 0;
-        if (hipHostMalloc(&env->stage, need, hipHostMallocDefault) != hipSuccess) { env->stage = nullptr; return fail("pgr_fan_fetch_rays_compact: host allocation failed"); }
-        env->stage_bytes = need;
-    }
+    if (!grow_buffer(env->stage, env->stage_bytes, need, true)) return fail("pgr_fan_fetch_rays_compact: host allocation failed");
     char* sb = (char*)env->stage;
     const double* h_end = (const double*)sb;
     const int32_t* h_nb = (const int32_t*)(sb + n * 24);
     const int32_t* h_ns = (const int32_t*)(sb + n * 28);
     hipStream_t st = f->stream;
-    if (end_state) HIPCHK(hipMemcpyAsync((void*)h_end, f->end, n * 24, hipMemcpyDeviceToHost, st));
-    if (n_bott) HIPCHK(hipMemcpyAsync((void*)h_nb, f->nb, n * 4, hipMemcpyDeviceToHost, st));
-    if (n_surf) HIPCHK(hipMemcpyAsync((void*)h_ns, f->ns, n * 4, hipMemcpyDeviceToHost, st));
+    if (end_state) HIPCHK(hipMemcpyAsync((void*)h_end, f->d.end, n * 24, hipMemcpyDeviceToHost, st));
+    if (n_bott) HIPCHK(hipMemcpyAsync((void*)h_nb, f->d.nb, n * 4, hipMemcpyDeviceToHost, st));
+    if (n_surf) HIPCHK(hipMemcpyAsync((void*)h_ns, f->d.ns, n * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     unsigned nt = std::thread::hardware_concurrency();
     nt = nt < 1 ? 1 : (nt > 8 ? 8 : nt);
@@ -295,10 +276,9 @@ extern "C" int pgr_fan_fetch_samples(pgr_fan* f, double* T, double* z, double* p
     const bool compact = (flags & PGR_COMPACT) != 0;
     const size_t ns_bytes = (size_t)f->N * (size_t)f->S * sizeof(double);   // (what reaches the caller: [S][N], or less)
     std::vector<D2HJob> jobs;
-    std::vector<const double*> src;
-    if (T) { jobs.push_back({T, f->T, ns_bytes}); src.push_back(f->T); }
-    if (z) { jobs.push_back({z, f->Z, ns_bytes}); src.push_back(f->Z); }
-    if (p) { jobs.push_back({p, f->P, ns_bytes}); src.push_back(f->P); }
+    if (T) jobs.push_back({T, f->d.T, ns_bytes});
+    if (z) jobs.push_back({z, f->d.Z, ns_bytes});
+    if (p) jobs.push_back({p, f->d.P, ns_bytes});
     if (jobs.empty()) return 0;
     hipStream_t st = f->stream;
     auto ready = [&](std::vector<D2HJob>& jb) -> int {
@@ -307,34 +287,9 @@ extern "C" int pgr_fan_fetch_samples(pgr_fan* f, double* T, double* z, double* p
         const bool squeeze = compact && f->M != f->N;
         if (!squeeze && !f->blocked) return 0;
         const int64_t M = squeeze ? f->M : f->N;
-        const size_t mbytes = (size_t)f->S * (size_t)M * sizeof(double), piece = (mbytes + 255) & ~(size_t)255;
-        if (M > 0) {
-            const size_t need = jb.size() * piece + (((size_t)M * sizeof(int) + 255) & ~(size_t)255);
-            if (need > f->scratch_bytes) {
-                if (f->scratch) (void)hipFree(f->scratch);
-                f->scratch = nullptr; f->scratch_bytes = 0;
-                if (hipMalloc(&f->scratch, need) != hipSuccess) { f->scratch = nullptr; return fail("pgr_fan_fetch_samples: device allocation of the un-blocking scratch failed"); }
-                f->scratch_bytes = need;
-            }
-            int* didx = nullptr;
-            if (squeeze) {
-                didx = (int*)((char*)f->scratch + jb.size() * piece);
-                HIPCHK(hipMemcpyAsync(didx, f->keep.data(), (size_t)M * sizeof(int), hipMemcpyHostToDevice, st));
-            }
-            for (size_t a3 = 0; a3 < jb.size(); a3++) {
-                double* t = (double*)((char*)f->scratch + a3 * piece);
-                if (f->blocked)
-                    hipLaunchKernelGGL(pgr_unblock_cols, dim3((unsigned)((M + 255) / 256), (unsigned)((f->S + 3) / 4)), dim3(256), 0, st,
-                                       (const double*)jb[a3].src, t, (const int*)didx, M, f->N, (int)f->S);
-                else
-                    hipLaunchKernelGGL(pgr_gather_cols, dim3((unsigned)((M + 255) / 256), (unsigned)f->S), dim3(256), 0, st,
-                                       (const double*)jb[a3].src, t, (const int*)didx, M, f->N);
-                HIPCHK(hipGetLastError());
-                jb[a3].src = t;
-            }
-        }
-        for (auto& q : jb) q.bytes = mbytes;
-        return 0;
+        if (!grow_buffer(f->scratch, f->scratch_bytes, squeeze_bytes(jb.size(), M, f->S)))
+            return fail("pgr_fan_fetch_samples: device allocation of the un-blocking scratch failed");
+        return squeeze_rows(jb, f->blocked, squeeze ? f->keep.data() : nullptr, M, f->N, f->S, f->scratch, st);
     };
     return d2h_pipelined(jobs, st, f->env->device, ready);
 }

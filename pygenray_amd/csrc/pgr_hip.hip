@@ -45,7 +45,7 @@
 // the rest of this translation unit, in dependency order (one TU: the instruction-layout pass of the build works on ONE
 // device object, and the kernels' order in it is part of what device_code_sha256 names)
 #include "pgr_aux_kernels.h"    // wave cost / placement kernels, unit-level test kernels
-#include "pgr_host.h"           // error handling, struct pgr_env, pgr_build_info
+#include "pgr_host.h"           // error handling, struct pgr_env, buffers, fan buffer layout, pgr_build_info
 #include "pgr_env.h"            // environment construction + host-side verification, options, queries
 #include "pgr_launch.h"         // wave scheduling, pgr_shoot_fan_device
 #include "pgr_transfer.h"       // compaction, pipelined D2H, pgr_shoot_fan

@@ -1,5 +1,6 @@
-// pgr_host.h -- host side, common part: error string, PGR_TRACE marks, HIPCHK, the environment object (struct pgr_env) and what the
-// library says about its own build (pgr_build_info).
+// pgr_host.h -- host side, common part: error string, PGR_TRACE marks, HIPCHK, the environment object (struct pgr_env) and its
+// stream, grow-only and scoped buffers, the layout of a fan's device buffers (FanBufs), np.linspace's save ranges, and what
+// the library says about its own build (pgr_build_info).
 // (Part of the ONE translation unit pgr_hip.hip, included there in this order; not a stand-alone header.)
 #ifndef PGR_HOST_H
 #define PGR_HOST_H
@@ -41,10 +42,10 @@ struct pgr_env {
     int place = 2;                    // 0 off, 1 issue priorities only, 2 cost-aware placement + priorities
     int api_blocked = 1;              // host-pointer entry / fan handles: HBM-table trajectory fans run the sample-blocked kernel (un-blocked on the way out)
     int persistent = 1;               // fans of several rounds: persistent waves claiming packets from the cost-sorted list (0: whole workgroups, static)
-    hipStream_t stream = nullptr;     // the host-pointer entry's own stream (created on first use)
+    hipStream_t stream = nullptr;     // the host-pointer entry's own stream (env_stream: created on first use)
     EnvDev d{};
     const EnvDev* d_dev = nullptr;  // device copy of `d` (kernel argument by pointer)
-    // grow-only staging workspace of the host-pointer entry (kept while <= 256 MB so the many
+    // grow-only staging workspace of the host-pointer entry and of the eigenray loop (kept while <= 16 GB so the many
     // small fans of an eigenray search do not pay 11 hipMalloc/hipFree per call)
     void* ws = nullptr;
     size_t ws_bytes = 0;
@@ -58,7 +59,7 @@ struct pgr_env {
     bool doomed = false;
     void* stage = nullptr;   // page-locked host staging of the compacted per-ray fetch (grow-only)
     size_t stage_bytes = 0;
-    void* ws2 = nullptr;   // second grow-only workspace: the compacted trajectories of PGR_COMPACT
+    void* ws2 = nullptr;   // second grow-only workspace: the squeezed trajectories (un-blocked, or compacted by PGR_COMPACT)
     size_t ws2_bytes = 0;
     std::mutex ws_mutex;
     // small buffers for the per-launch wave placement (cost[waves] + map[slots]): a slot is handed to a launch and
@@ -87,6 +88,79 @@ struct pgr_env {
 };
 
 extern "C" const char* pgr_last_error(void) { return g_err.c_str(); }
+
+// the environment's own stream, created on first use (callers that hold ws_mutex create it before they take the lock)
+static int env_stream(pgr_env* env)
+{
+    if (env->stream) return 0;
+    std::lock_guard<std::mutex> lock(env->ws_mutex);
+    if (!env->stream) HIPCHK(hipStreamCreateWithFlags(&env->stream, hipStreamNonBlocking));
+    return 0;
+}
+
+// Grow-only buffer (device memory, page-locked host memory with `host`): kept when it holds `bytes` already, else freed and
+// allocated anew.  A failed allocation leaves (nullptr, 0), clears the HIP error state and returns false.
+static bool grow_buffer(void*& p, size_t& have, size_t bytes, bool host = false)
+{
+    if (bytes <= have) return true;
+    if (p) (void)(host ? hipHostFree(p) : hipFree(p));
+    have = 0;
+    if ((host ? hipHostMalloc(&p, bytes, hipHostMallocDefault) : hipMalloc(&p, bytes)) == hipSuccess) { have = bytes; return true; }
+    p = nullptr;
+    (void)hipGetLastError();
+    return false;
+}
+
+// scoped device buffer (the debug entries)
+struct DevBuf {
+    void* p = nullptr;
+    ~DevBuf() { if (p) (void)hipFree(p); }
+    int alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8) == hipSuccess ? 0 : -1; }
+};
+
+// One block cut into consecutive 256-byte aligned pieces.  The same cuts run twice: with base == nullptr for the block's
+// size (`total`; the pointers stay null), then on the block itself.
+struct Carve {
+    char* base = nullptr;
+    size_t total = 0;
+    template <class T> T* take(size_t count)
+    {
+        const size_t o = total;
+        total += (count * sizeof(T) + 255) & ~(size_t)255;
+        return base ? (T*)(base + o) : nullptr;
+    }
+};
+
+// A fan's device buffers (the host-pointer entry's workspace, a pgr_fan handle's block), in their order in the block
+struct FanBufs {
+    double *y0, *r, *T, *Z, *P, *end;
+    int32_t *nb, *ns, *st, *n1, *n2;
+};
+
+// y0 [N][3]; r [S] (one double without trajectories); T, Z, P [S][N] (sample-blocked: [ceil(S/4)][N][4]); end [N][3];
+// n_bott, n_surf, status, n_steps, n_rej [N].  `bytes`: the block's size.
+static FanBufs fan_carve(void* base, int64_t N, int32_t S, bool save, bool blocked, size_t* bytes = nullptr)
+{
+    const size_t n = (size_t)N, ns = !save ? 0 : n * (size_t)(blocked ? 4 * ((S + 3) / 4) : S);
+    Carve c{(char*)base};
+    FanBufs b;
+    b.y0 = c.take<double>(3 * n); b.r = c.take<double>(save ? (size_t)S : 1);
+    b.T = c.take<double>(ns); b.Z = c.take<double>(ns); b.P = c.take<double>(ns); b.end = c.take<double>(3 * n);
+    b.nb = c.take<int32_t>(n); b.ns = c.take<int32_t>(n); b.st = c.take<int32_t>(n); b.n1 = c.take<int32_t>(n); b.n2 = c.take<int32_t>(n);
+    if (bytes) *bytes = c.total;
+    return b;
+}
+
+static size_t fan_bytes(int64_t N, int32_t S, bool save, bool blocked) { size_t b = 0; fan_carve(nullptr, N, S, save, blocked, &b); return b; }
+
+// np.linspace(x0, x1, S)[j] to the bit: j * step + x0 (the last one x1), the product rounded before the sum whatever the
+// host compiler's contraction setting
+static double linspace_at(double x0, double x1, int32_t S, int32_t j)
+{
+    if (S > 1 && j == S - 1) return x1;
+    volatile double m = (double)j * (S > 1 ? (x1 - x0) / (double)(S - 1) : 0.0);
+    return m + x0;
+}
 
 // What the build did to this library: the second pass of the build (pygenray_amd/_isa_layout.py, run
 // by pygenray_amd/_lib.py) re-encodes the device code and, when it has succeeded, overwrites this tag

@@ -1,5 +1,5 @@
 // pgr_launch.h -- launching a fan: per-launch wave scheduling (placement slots, pgr_wave_cost / pgr_wave_place) and pgr_shoot_fan_device --
-// kernel-instance selection, LDS budget, the launch itself.
+// kernel-instance selection, LDS budget, the launch itself; whether the host entries run a fan sample-blocked (fan_blocked).
 // (Part of the ONE translation unit pgr_hip.hip, included there in this order; not a stand-alone header.)
 #ifndef PGR_LAUNCH_H
 #define PGR_LAUNCH_H
@@ -50,13 +50,8 @@ static int schedule_waves(pgr_env* env, const double* y0, int64_t N, int64_t wav
         HIPCHK(hipEventCreateWithFlags(&env->place_slots[pick].ev, hipEventDisableTiming));
     }
     pgr_env::PlaceSlot& ps = env->place_slots[pick];
-    if (need > ps.bytes) {
-        if (ps.buf) (void)hipFree(ps.buf);    // (not in flight: nobody reads it)
-        ps.buf = nullptr; ps.bytes = 0;
-        const size_t sz = need > 65536 ? need : 65536;
-        HIPCHK(hipMalloc(&ps.buf, sz));
-        ps.bytes = sz;
-    }
+    // (the slot is not in flight: nobody reads its buffer)
+    if (need > ps.bytes && !grow_buffer(ps.buf, ps.bytes, need > 65536 ? need : 65536)) return fail("pgr_shoot_fan: device allocation of the wave placement failed");
     ps.in_flight = true;   // (the event is recorded by the caller behind the fan kernel: PlaceGuard)
     ps.recorded = false;
     slot_out = pick;
@@ -123,6 +118,13 @@ static bool blocked_layout_fits(const pgr_env* env)
     if (lds_tab || !env->api_blocked) return false;
     const size_t at = ((((zx_bytes + 15) & ~(size_t)15) + (size_t)env->d.nb * 16) + 15) & ~(size_t)15;
     return at + 8 * 6144 <= env->max_lds;
+}
+
+// Does a fan of these flags, launched by the host-pointer entry or a fan handle, run sample-blocked (un-blocked on the way
+// out)?  Trajectories on a linspace grid in the default sample form, sample-major, and an environment it fits.
+static bool fan_blocked(const pgr_env* env, bool save, uint32_t flags)
+{
+    return save && (flags & PGR_SAVE_LINSPACE) && (flags & PGR_SAMPLE_MAJOR) && !(flags & PGR_EXACT_SAMPLES) && blocked_layout_fits(env);
 }
 
 extern "C" int pgr_shoot_fan_device(pgr_env* env, const double* y0, int64_t N, double source_range,
@@ -311,13 +313,5 @@ extern "C" int pgr_debug_last_instance(const pgr_env* env, int32_t out[8])
     for (int q = 0; q < 8; q++) out[q] = env->last_instance[q].load(std::memory_order_relaxed);
     return 0;
 }
-
-namespace {
-struct DevBuf {
-    void* p = nullptr;
-    ~DevBuf() { if (p) (void)hipFree(p); }
-    int alloc(size_t bytes) { return hipMalloc(&p, bytes ? bytes : 8) == hipSuccess ? 0 : -1; }
-};
-}  // namespace
 
 #endif  // PGR_LAUNCH_H

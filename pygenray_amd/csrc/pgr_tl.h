@@ -192,18 +192,17 @@ extern "C" int pgr_fan_intensity(pgr_fan* f, const double* p0, const double* dep
         HIPCHK(hipMemcpy(f->d_keep, f->keep.data(), (size_t)f->M * sizeof(int), hipMemcpyHostToDevice));
     }
     if (!f->r_filled) {
-        // the save ranges as the fan kernel forms them (PGR_SAVE_LINSPACE: x0 + j * step, the last one x1 -- np.linspace's bits)
+        // the save ranges, np.linspace's bits (PGR_SAVE_LINSPACE: the fan kernel's for S > 1; at S = 1 the one column is NaN)
         std::vector<double> r((size_t)f->S);
-        const double step = f->S > 1 ? (f->x1 - f->x0) / (double)(f->S - 1) : 0.0;
-        for (int32_t k = 0; k < f->S; k++) r[(size_t)k] = (k >= f->S - 1) ? f->x1 : f->x0 + (double)k * step;
-        HIPCHK(hipMemcpy(f->r, r.data(), (size_t)f->S * sizeof(double), hipMemcpyHostToDevice));
+        for (int32_t k = 0; k < f->S; k++) r[(size_t)k] = linspace_at(f->x0, f->x1, f->S, k);
+        HIPCHK(hipMemcpy(f->d.r, r.data(), (size_t)f->S * sizeof(double), hipMemcpyHostToDevice));
         f->r_filled = true;
     }
     TlArgs a{};
-    a.Z = f->Z; a.P = f->P; a.keep = (f->M != f->N) ? f->d_keep : nullptr;
+    a.Z = f->d.Z; a.P = f->d.P; a.keep = (f->M != f->N) ? f->d_keep : nullptr;
     a.N = f->N; a.M = f->M; a.S = f->S; a.blocked = f->blocked ? 1 : 0;
     a.zsign = (f->flags & PGR_STORED_SIGN) ? -1.0 : 1.0;
-    a.x = f->r; a.p0 = p0; a.depths = depths; a.R = n_depths; a.out = out;
+    a.x = f->d.r; a.p0 = p0; a.depths = depths; a.R = n_depths; a.out = out;
     return tl_run(f->env, a, (hipStream_t)stream, "pgr_fan_intensity");
 }
 

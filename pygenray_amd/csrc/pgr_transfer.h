@@ -1,5 +1,6 @@
-// pgr_transfer.h -- results to the host: compaction of dropped rays on the device, the D2H copy pipelined with the page faults of the
-// caller's buffers, and the host-pointer entry pgr_shoot_fan built on both.
+// pgr_transfer.h -- results to the host: the squeeze of trajectories into [S][M] rows on the device (un-blocking, compaction of
+// dropped rays; both host entries), the D2H copy pipelined with the page faults of the caller's buffers, and the host-pointer
+// entry pgr_shoot_fan built on both.
 // (Part of the ONE translation unit pgr_hip.hip, included there in this order; not a stand-alone header.)
 #ifndef PGR_TRANSFER_H
 #define PGR_TRANSFER_H
@@ -228,6 +229,41 @@ static int d2h_pipelined(std::vector<D2HJob> jobs, hipStream_t st, int device, R
     return 0;
 }
 
+// The squeeze of trajectories into [S][M] rows before their D2H copy (both host entries): a sample-blocked source is
+// un-blocked (pgr_unblock_cols), a row source loses its dropped rays (pgr_gather_cols).  `keep`: the host list of the M
+// surviving rays' columns (nullptr: every ray, M = N).  `scratch` holds
+// squeeze_bytes(jobs.size(), M, S): the rows of each job, then the uploaded index list.  Each job's source becomes its rows.
+static size_t squeeze_bytes(size_t arrays, int64_t M, int32_t S)
+{
+    return arrays * (((size_t)S * (size_t)M * sizeof(double) + 255) & ~(size_t)255) + (((size_t)M * sizeof(int) + 255) & ~(size_t)255);
+}
+
+static int squeeze_rows(std::vector<D2HJob>& jobs, bool blocked, const int* keep, int64_t M, int64_t N, int32_t S,
+                        void* scratch, hipStream_t st)
+{
+    const size_t rows = (size_t)S * (size_t)M * sizeof(double), piece = (rows + 255) & ~(size_t)255;
+    if (M > 0) {
+        int* didx = nullptr;
+        if (keep) {
+            didx = (int*)((char*)scratch + jobs.size() * piece);
+            HIPCHK(hipMemcpyAsync(didx, keep, (size_t)M * sizeof(int), hipMemcpyHostToDevice, st));
+        }
+        for (size_t a = 0; a < jobs.size(); a++) {
+            double* dst = (double*)((char*)scratch + a * piece);
+            if (blocked)
+                hipLaunchKernelGGL(pgr_unblock_cols, dim3((unsigned)((M + 255) / 256), (unsigned)((S + 3) / 4)), dim3(256), 0, st,
+                                   (const double*)jobs[a].src, dst, (const int*)didx, M, N, (int)S);
+            else    // (a row source always comes with its index list)
+                hipLaunchKernelGGL(pgr_gather_cols, dim3((unsigned)((M + 255) / 256), (unsigned)S), dim3(256), 0, st,
+                                   (const double*)jobs[a].src, dst, (const int*)didx, M, N);
+            HIPCHK(hipGetLastError());
+            jobs[a].src = dst;
+        }
+    }
+    for (auto& q : jobs) q.bytes = rows;
+    return 0;
+}
+
 extern "C" int pgr_shoot_fan(pgr_env* env, const double* y0, int64_t N, double source_range,
                              double receiver_range, const double* r_save, int32_t S, double rtol,
                              double atol, uint32_t flags, int64_t max_steps, double* T, double* z,
@@ -243,56 +279,30 @@ extern "C" int pgr_shoot_fan(pgr_env* env, const double* y0, int64_t N, double s
     // (the blocked layout is a device-side layout: its buffers hold 4 ceil(S/4) N doubles, this entry's hold S N)
     if (flags & PGR_SAMPLE_BLOCKED) return fail("pgr_shoot_fan: PGR_SAMPLE_BLOCKED is for pgr_shoot_fan_device (device-resident consumers)");
     HIPCHK(hipSetDevice(env->device));
+    // everything of this call goes through the environment's own stream and waits for THAT stream only
+    // (not the device: other streams of the process -- another environment's fan, a framework's copies --
+    // are none of its business)
+    if (env_stream(env)) return -1;
     std::lock_guard<std::mutex> lock(env->ws_mutex);
     size_t ns_bytes = (size_t)N * (size_t)(save ? S : 0) * sizeof(double);
     // is r_save exactly np.linspace(source_range, receiver_range, S)?  then the kernel recomputes it per index instead
     // of loading it
-    bool lin = save;
     if (save) {
-        const double step = (S > 1) ? (receiver_range - source_range) / (double)(S - 1) : 0.0;
-        for (int32_t j = 0; j < S && lin; j++) {
-            volatile double m = (double)j * step;
-            volatile double v = m + source_range;
-            double want = (j == S - 1 && S > 1) ? receiver_range : (double)v;
-            lin = (r_save[j] == want);
-        }
+        bool lin = true;
+        for (int32_t j = 0; j < S && lin; j++) lin = (r_save[j] == linspace_at(source_range, receiver_range, S, j));
         if (lin) flags |= PGR_SAVE_LINSPACE; else flags &= ~PGR_SAVE_LINSPACE;
     }
     // Environments whose tables stay in HBM / L2: the trajectories are integrated by the sample-blocked kernel (device
     // buffers [ceil(S/4)][N][4]) and un-blocked to the caller's [S][N] / [S][M] by the pass that squeezes dropped rays out
-    bool blocked = save && lin && (flags & PGR_SAMPLE_MAJOR) && !(flags & PGR_EXACT_SAMPLES) && blocked_layout_fits(env) &&
-                   N <= 0x7fffffff;
-    if (blocked) {
-        // ... which needs a second workspace of 3 S N doubles beside the blocked buffers.  It is obtained HERE, before
-        // anything is launched: if the device cannot give it, the fan runs the plain row kernel straight into the
-        // caller's layout instead (same bits, 2.3 x the store traffic) -- the blocked path never fails a call that the row
-        // path would have served
-        const size_t piece = ((size_t)S * (size_t)N * sizeof(double) + 255) & ~(size_t)255;
-        const size_t need2 = 3 * piece + (((size_t)N * 4 + 255) & ~(size_t)255) + 256;
-        if (need2 > env->ws2_bytes) {
-            if (env->ws2) (void)hipFree(env->ws2);
-            env->ws2 = nullptr; env->ws2_bytes = 0;
-            if (hipMalloc(&env->ws2, need2) == hipSuccess) env->ws2_bytes = need2;
-            else { env->ws2 = nullptr; (void)hipGetLastError(); blocked = false; }
-        }
-    }
-    const size_t dev_ns_bytes = blocked ? (size_t)N * (size_t)(4 * ((S + 3) / 4)) * sizeof(double) : ns_bytes;
+    // ... which needs a second workspace of 3 S N doubles beside the blocked buffers.  It is obtained HERE, before
+    // anything is launched: if the device cannot give it, the fan runs the plain row kernel straight into the
+    // caller's layout instead (same bits, 2.3 x the store traffic) -- the blocked path never fails a call that the row
+    // path would have served
+    bool blocked = fan_blocked(env, save, flags) && N <= 0x7fffffff;
+    if (blocked && !grow_buffer(env->ws2, env->ws2_bytes, squeeze_bytes(3, N, S))) blocked = false;
     // carve one workspace: y0, r_save, T, Z, P, end, 5 int arrays (256-byte aligned pieces)
-    const size_t sizes[11] = {(size_t)N * 24, (size_t)(save ? S : 1) * 8, dev_ns_bytes, dev_ns_bytes, dev_ns_bytes,
-                              (size_t)N * 24, (size_t)N * 4, (size_t)N * 4, (size_t)N * 4, (size_t)N * 4,
-                              (size_t)N * 4};
-    size_t off[11], total = 0;
-    for (int k = 0; k < 11; k++) { off[k] = total; total += (sizes[k] + 255) & ~(size_t)255; }
-    if (total > env->ws_bytes) {
-        if (env->ws) (void)hipFree(env->ws);
-        env->ws = nullptr; env->ws_bytes = 0;
-        if (hipMalloc(&env->ws, total) != hipSuccess) { env->ws = nullptr; return fail("pgr_shoot_fan: device allocation failed"); }
-        env->ws_bytes = total;
-    }
-    struct Piece { void* p; } dy0{(char*)env->ws + off[0]}, dr{(char*)env->ws + off[1]}, dT{(char*)env->ws + off[2]},
-        dZ{(char*)env->ws + off[3]}, dP{(char*)env->ws + off[4]}, dE{(char*)env->ws + off[5]},
-        dnb{(char*)env->ws + off[6]}, dns{(char*)env->ws + off[7]}, dst{(char*)env->ws + off[8]},
-        dn1{(char*)env->ws + off[9]}, dn2{(char*)env->ws + off[10]};
+    if (!grow_buffer(env->ws, env->ws_bytes, fan_bytes(N, S, save, blocked))) return fail("pgr_shoot_fan: device allocation failed");
+    const FanBufs d = fan_carve(env->ws, N, S, save, blocked);
     struct Trim {  // give a very large workspace (> 16 GB of the 288 GB) back when the call ends
         pgr_env* e;
         ~Trim()
@@ -301,75 +311,45 @@ extern "C" int pgr_shoot_fan(pgr_env* env, const double* y0, int64_t N, double s
             if (e->ws2_bytes > ((size_t)16 << 30)) { (void)hipFree(e->ws2); e->ws2 = nullptr; e->ws2_bytes = 0; }
         }
     } trim{env};
-    // everything of this call goes through the environment's own stream and waits for THAT stream only
-    // (not the device: other streams of the process -- another environment's fan, a framework's copies --
-    // are none of its business)
-    if (!env->stream) HIPCHK(hipStreamCreateWithFlags(&env->stream, hipStreamNonBlocking));
     hipStream_t st = env->stream;
-    HIPCHK(hipMemcpyAsync(dy0.p, y0, N * 3 * sizeof(double), hipMemcpyHostToDevice, st));
-    if (save) HIPCHK(hipMemcpyAsync(dr.p, r_save, (size_t)S * sizeof(double), hipMemcpyHostToDevice, st));
-    int rc = pgr_shoot_fan_device(env, (const double*)dy0.p, N, source_range, receiver_range,
-                                  (const double*)dr.p, S, rtol, atol, flags | (blocked ? PGR_SAMPLE_BLOCKED : 0u), max_steps,
-                                  save ? (double*)dT.p : nullptr, save ? (double*)dZ.p : nullptr,
-                                  save ? (double*)dP.p : nullptr, (double*)dE.p, (int32_t*)dnb.p,
-                                  (int32_t*)dns.p, (int32_t*)dst.p, (int32_t*)dn1.p, (int32_t*)dn2.p,
-                                  (void*)st);
+    HIPCHK(hipMemcpyAsync(d.y0, y0, N * 3 * sizeof(double), hipMemcpyHostToDevice, st));
+    if (save) HIPCHK(hipMemcpyAsync(d.r, r_save, (size_t)S * sizeof(double), hipMemcpyHostToDevice, st));
+    int rc = pgr_shoot_fan_device(env, d.y0, N, source_range, receiver_range, d.r, S, rtol, atol,
+                                  flags | (blocked ? PGR_SAMPLE_BLOCKED : 0u), max_steps, save ? d.T : nullptr,
+                                  save ? d.Z : nullptr, save ? d.P : nullptr, d.end, d.nb, d.ns, d.st, d.n1, d.n2, (void*)st);
     if (rc) return rc;
     // The per-ray arrays are small; the trajectories go out through the pipelined copy (page faults of the caller's
     // -- typically fresh -- buffers in order on helper threads, starting now, while the kernel runs; copies as soon as
     // the kernel is done and a piece's pages are there).  PGR_COMPACT: dropped rays are squeezed out on the device
     // first ([S][N] -> [S][M], one pass at HBM speed into a second grow-only workspace).
     std::vector<D2HJob> jobs;
-    if (save) jobs = {{T, dT.p, ns_bytes}, {z, dZ.p, ns_bytes}, {p, dP.p, ns_bytes}};
+    if (save) jobs = {{T, d.T, ns_bytes}, {z, d.Z, ns_bytes}, {p, d.P, ns_bytes}};
     std::vector<int> keep;   // (outlives the asynchronous upload of the index list)
     auto ready = [&](std::vector<D2HJob>& jb) -> int {
-        HIPCHK(hipMemcpyAsync(status, dst.p, N * 4, hipMemcpyDeviceToHost, st));
+        HIPCHK(hipMemcpyAsync(status, d.st, N * 4, hipMemcpyDeviceToHost, st));
         HIPCHK(hipStreamSynchronize(st));       // the kernel has finished
         const bool compact = save && (flags & PGR_COMPACT);
         if (!compact && !blocked) return 0;
         if (compact && !(flags & PGR_SAMPLE_MAJOR)) return fail("pgr_shoot_fan: PGR_COMPACT needs PGR_SAMPLE_MAJOR");
         if (N > 0x7fffffff) return fail("pgr_shoot_fan: PGR_COMPACT supports at most 2^31 - 1 rays per call");   // (compact only: the blocked path was decided with N in range)
-        int64_t M = N;
         if (compact) {
             keep.reserve((size_t)N);
             for (int64_t k = 0; k < N; k++) if (status[k] == 0) keep.push_back((int)k);
-            M = (int64_t)keep.size();
         }
+        const int64_t M = compact ? (int64_t)keep.size() : N;
         if (M == N && !blocked) return 0;
-        const size_t mbytes = (size_t)S * (size_t)M * sizeof(double), piece = (mbytes + 255) & ~(size_t)255;
-        const size_t need2 = 3 * piece + (((size_t)M * 4 + 255) & ~(size_t)255) + 256;
-        if (need2 > env->ws2_bytes) {
-            if (env->ws2) (void)hipFree(env->ws2);
-            env->ws2 = nullptr; env->ws2_bytes = 0;
-            if (hipMalloc(&env->ws2, need2) != hipSuccess) { env->ws2 = nullptr; return fail("pgr_shoot_fan: device allocation of the PGR_COMPACT workspace failed"); }
-            env->ws2_bytes = need2;
-        }
-        int* didx = (int*)((char*)env->ws2 + 3 * piece);
-        if (M > 0) {
-            const bool all = (M == N);     // (blocked and nothing dropped, or no compaction asked for: un-block every ray)
-            if (!all) HIPCHK(hipMemcpyAsync(didx, keep.data(), (size_t)M * sizeof(int), hipMemcpyHostToDevice, st));
-            for (int a3 = 0; a3 < 3; a3++) {
-                double* tmp = (double*)((char*)env->ws2 + (size_t)a3 * piece);
-                if (blocked)
-                    hipLaunchKernelGGL(pgr_unblock_cols, dim3((unsigned)((M + 255) / 256), (unsigned)((S + 3) / 4)), dim3(256), 0, st,
-                                       (const double*)jb[a3].src, tmp, all ? (const int*)nullptr : (const int*)didx, M, N, (int)S);
-                else
-                    hipLaunchKernelGGL(pgr_gather_cols, dim3((unsigned)((M + 255) / 256), (unsigned)S), dim3(256), 0, st,
-                                       (const double*)jb[a3].src, tmp, (const int*)didx, M, N);
-                HIPCHK(hipGetLastError());
-                jb[a3].src = tmp;
-            }
-        }
-        for (int a3 = 0; a3 < 3; a3++) jb[a3].bytes = mbytes;
-        return 0;
+        // (the blocked path reserved this before the launch: M <= N, nothing is allocated here)
+        if (!grow_buffer(env->ws2, env->ws2_bytes, squeeze_bytes(3, M, S)))
+            return fail("pgr_shoot_fan: device allocation of the PGR_COMPACT workspace failed");
+        return squeeze_rows(jb, blocked, M < N ? keep.data() : nullptr, M, N, S, env->ws2, st);
     };
     rc = d2h_pipelined(jobs, st, env->device, ready);
     if (rc) return rc;
-    if (end_state) HIPCHK(hipMemcpyAsync(end_state, dE.p, N * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(n_bott, dnb.p, N * 4, hipMemcpyDeviceToHost, st));
-    HIPCHK(hipMemcpyAsync(n_surf, dns.p, N * 4, hipMemcpyDeviceToHost, st));
-    if (n_steps) HIPCHK(hipMemcpyAsync(n_steps, dn1.p, N * 4, hipMemcpyDeviceToHost, st));
-    if (n_rej) HIPCHK(hipMemcpyAsync(n_rej, dn2.p, N * 4, hipMemcpyDeviceToHost, st));
+    if (end_state) HIPCHK(hipMemcpyAsync(end_state, d.end, N * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(n_bott, d.nb, N * 4, hipMemcpyDeviceToHost, st));
+    HIPCHK(hipMemcpyAsync(n_surf, d.ns, N * 4, hipMemcpyDeviceToHost, st));
+    if (n_steps) HIPCHK(hipMemcpyAsync(n_steps, d.n1, N * 4, hipMemcpyDeviceToHost, st));
+    if (n_rej) HIPCHK(hipMemcpyAsync(n_rej, d.n2, N * 4, hipMemcpyDeviceToHost, st));
     HIPCHK(hipStreamSynchronize(st));
     return 0;
 }
