@@ -269,6 +269,37 @@ int pgr_intensity_device(pgr_env* env, const double* z, const double* p, int64_t
                          const double* x, const double* p0, const double* depths, int64_t n_depths, double* out,
                          void* stream);
 
+/* Ray-tube arrivals at receiver depths ("Arrivals"): every tube k that pgr_fan_intensity adds at receiver j
+ * and save column s -- the same validity and [lo, hi) tests, none added, none left out -- is one arrival, with
+ *   w = (D_j - d_k) / (d_k+1 - d_k),   T = T_k + w (T_k+1 - T_k),   p = p_k + w (p_k+1 - p_k)   (p: stored sign),
+ * I = the tube's term of the intensity sum (the same bits) and tube = k (rays k, k + 1 of the surviving rays).
+ * cols[n_cols] (HOST, int32, each 0 .. S - 1, repeats allowed, 1 <= n_cols <= 65535): the columns asked for, slot c being
+ * column cols[c].  The column r_s == 0 has no arrivals.  Two calls with the same arguments:
+ *
+ * pgr_fan_arrival_counts: counts[j * n_cols + c] (DEVICE int64, [n_depths][n_cols], overwritten) = the arrivals of
+ *   receiver j at slot c.
+ * pgr_fan_arrivals: offsets[j * n_cols + c] (DEVICE int64) = where those arrivals start, the exclusive scan of the counts;
+ *   each receiver's arrivals at each slot are written there in increasing k into tube (int32), w, T, p, I (DEVICE,
+ *   n_arrivals >= 1 entries each; nothing is written at or past n_arrivals).
+ *
+ * Deterministic: no atomics, one lane finds and writes one receiver's arrivals in tube order.  Fan arguments, waiting and
+ * streams as pgr_fan_intensity. */
+int pgr_fan_arrival_counts(pgr_fan* fan, const double* p0, const double* depths, int64_t n_depths, const int32_t* cols,
+                           int32_t n_cols, int64_t* counts, void* stream);
+int pgr_fan_arrivals(pgr_fan* fan, const double* p0, const double* depths, int64_t n_depths, const int32_t* cols,
+                     int32_t n_cols, const int64_t* offsets, int64_t n_arrivals, int32_t* tube, double* w, double* T,
+                     double* p, double* I, void* stream);
+
+/* The same for caller buffers, as pgr_intensity_device: T, z, p (DEVICE) [n_samples][n_rays] rows, stored sign
+ * convention, every ray a tube edge; x[n_samples] (DEVICE) the save ranges in the frame of `env`.  The counts need no T. */
+int pgr_arrival_counts_device(pgr_env* env, const double* z, const double* p, int64_t n_rays, int32_t n_samples,
+                              const double* x, const double* p0, const double* depths, int64_t n_depths,
+                              const int32_t* cols, int32_t n_cols, int64_t* counts, void* stream);
+int pgr_arrivals_device(pgr_env* env, const double* T, const double* z, const double* p, int64_t n_rays,
+                        int32_t n_samples, const double* x, const double* p0, const double* depths, int64_t n_depths,
+                        const int32_t* cols, int32_t n_cols, const int64_t* offsets, int64_t n_arrivals, int32_t* tube,
+                        double* w, double* T_out, double* p_out, double* I, void* stream);
+
 /* Tuning options of ONE environment (per-ray results never depend on them; there is no process-wide
  * state: host threads that drive different GPUs hold different environments).
  *   PGR_OPT_WAVES_PER_BLOCK  a = waves (of 64 rays) per workgroup, 0 = automatic

@@ -1,0 +1,163 @@
+"""``arrivals``: the ray-tube arrivals of a fan at receiver depths ("Arrivals").
+
+Every ray tube that ``transmission_loss`` counts at a receiver and save range is one arrival, with its travel time and
+slowness interpolated across the tube.  The walk runs in HIP (csrc/pgr_arrivals.h) on the fan's trajectories where they
+already are -- in HBM for a device-resident fan, uploaded through torch for a host fan.  There is no CPU path.
+"""
+import numpy as np
+
+from . import _lib
+from .transmission import _FanFrame
+
+
+def _columns(range_indices, S):
+    """range_indices -> int32 column indices in 0 .. S - 1 (negative ones counted from the end)."""
+    if range_indices is None:
+        return np.array([S - 1], dtype=np.int32)
+    ri = np.atleast_1d(np.asarray(range_indices))
+    if ri.ndim != 1 or len(ri) == 0:
+        raise ValueError("range_indices must be a non-empty 1-D sequence of column indices")
+    if ri.dtype.kind not in "iu":
+        raise ValueError("range_indices must be integers")
+    if not np.all((ri >= -S) & (ri < S)):
+        raise ValueError(f"range_indices must lie in -{S} .. {S - 1} (the fan has {S} save ranges)")
+    if len(ri) > 65535:
+        raise ValueError("at most 65535 range_indices")
+    return np.ascontiguousarray(np.where(ri < 0, ri + S, ri), dtype=np.int32)
+
+
+def _bilinear(x, y, x_grid, y_grid, values):
+    """host_physics.bilinear_interp element-wise over arrays: the same cell rule and operations in the same order."""
+    i = np.clip(np.searchsorted(x_grid, x) - 1, 0, len(x_grid) - 2)
+    j = np.clip(np.searchsorted(y_grid, y) - 1, 0, len(y_grid) - 2)
+    wx = (x - x_grid[i]) / (x_grid[i + 1] - x_grid[i])
+    wy = (y - y_grid[j]) / (y_grid[j + 1] - y_grid[j])
+    return ((1 - wx) * (1 - wy) * values[i, j] + wx * (1 - wy) * values[i + 1, j]
+            + (1 - wx) * wy * values[i, j + 1] + wx * wy * values[i + 1, j + 1])
+
+
+class Arrivals:
+    """The arrivals of a fan at ``receiver_depths`` (R) and the requested save columns ``range_indices`` (n), host arrays.
+
+    Arrivals are grouped by receiver j, then by requested column c (the caller's order), then by increasing tube;
+    those of (j, c) are ``[offsets[j * n + c], offsets[j * n + c + 1])`` (``at(j, c)`` slices them).  Per arrival:
+
+    - ``tube``: index k into the fan's (surviving) rays; the tube is rays k and k + 1
+    - ``w``: (D_j - d_k) / (d_k+1 - d_k), where the receiver lies across the tube (0 <= w <= 1)
+    - ``time``: T_k + w (T_k+1 - T_k), seconds
+    - ``p``: p_k + w (p_k+1 - p_k), the slowness in ``RayFan.ps``'s sign convention
+    - ``intensity``: the tube's term of ``transmission_loss(..., intensity=True)``; summed in order from 0.0 it gives that
+      value at (j, c) bit for bit
+    - lazily: ``launch_angle`` (degrees, ``rays.thetas``' convention, interpolated by w), ``amplitude`` = sqrt(intensity),
+      ``received_angle`` = degrees(arcsin(p c(x, D_j))) with c from the tables of the frame the fan was traced in
+      (``host_physics.ray_angle``'s definition; ``EigenRays.received_angles`` uses the non-flat-earth table instead).
+
+    Bounce counts are known only at a ray's end: at the fan's last column, ``rays.n_surfs[tube]`` and
+    ``rays.n_botts[tube]`` apply.  The source's own column (r = 0) has no arrivals."""
+
+    def __init__(self, offsets, receiver_depths, ranges, range_indices, tube, w, time, p, intensity, thetas, c_rx):
+        self.offsets = offsets
+        self.receiver_depths = receiver_depths
+        self.ranges = ranges
+        self.range_indices = range_indices
+        self.tube = tube
+        self.w = w
+        self.time = time
+        self.p = p
+        self.intensity = intensity
+        self._thetas = thetas
+        self._c_rx = c_rx                      # (R, n) sound speed at the receivers, in the traced frame
+        self._lazy = {}
+
+    def __len__(self):
+        return len(self.tube)
+
+    def _pairs(self):
+        """(receiver, column slot) of every arrival"""
+        if "pairs" not in self._lazy:
+            n = len(self.range_indices)
+            idx = np.repeat(np.arange(len(self.offsets) - 1), np.diff(self.offsets))
+            self._lazy["pairs"] = (idx // n, idx % n)
+        return self._lazy["pairs"]
+
+    @property
+    def launch_angle(self):
+        if "launch_angle" not in self._lazy:
+            t0, t1 = self._thetas[self.tube], self._thetas[self.tube + 1]
+            self._lazy["launch_angle"] = t0 + self.w * (t1 - t0)
+        return self._lazy["launch_angle"]
+
+    @property
+    def amplitude(self):
+        if "amplitude" not in self._lazy:
+            self._lazy["amplitude"] = np.sqrt(self.intensity)
+        return self._lazy["amplitude"]
+
+    @property
+    def received_angle(self):
+        if "received_angle" not in self._lazy:
+            j, c = self._pairs()
+            with np.errstate(invalid="ignore"):
+                self._lazy["received_angle"] = np.degrees(np.arcsin(self.p * self._c_rx[j, c]))
+        return self._lazy["received_angle"]
+
+    def at(self, j, c):
+        """The arrivals at receiver j and requested column slot c -> dict of arrays (views)."""
+        n = len(self.range_indices)
+        if not (0 <= j < len(self.receiver_depths) and 0 <= c < n):
+            raise IndexError(f"(j, c) = ({j}, {c}) outside ({len(self.receiver_depths)}, {n})")
+        sl = slice(int(self.offsets[j * n + c]), int(self.offsets[j * n + c + 1]))
+        return dict(tube=self.tube[sl], w=self.w[sl], time=self.time[sl], p=self.p[sl], intensity=self.intensity[sl],
+                    launch_angle=self.launch_angle[sl], amplitude=self.amplitude[sl],
+                    received_angle=self.received_angle[sl])
+
+    def __repr__(self):
+        return (f"Arrivals({len(self)} arrivals at {len(self.receiver_depths)} receiver depths x "
+                f"{len(self.range_indices)} ranges)")
+
+
+def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=None, device=0):
+    """Ray-tube arrivals of ``rays`` (a ``RayFan`` from ``shoot_rays``) at ``receiver_depths`` (metres, positive down,
+    strictly ascending) and the save columns ``range_indices`` (default ``[S - 1]``, the receiver range; any integers in
+    -S .. S - 1) -> ``Arrivals``.
+
+    Every tube that ``transmission_loss`` counts at a receiver is one arrival: travel time and slowness interpolated
+    linearly in depth across the tube, the tube's intensity, its index into the fan.  The arguments, the frame (flat-earth,
+    mirrored for a backwards fan) and the sound speed are ``transmission_loss``'s.  A device-resident fan is processed
+    where it is and stays device resident."""
+    f = _FanFrame(rays, receiver_depths, environment, flatearth, "arrivals")
+    S = len(f.x)
+    cols = _columns(range_indices, S)
+    f.to_device(device)
+    import torch
+
+    R, n = len(f.depths), len(cols)
+    counts = torch.empty(R * n, dtype=torch.int64, device=f.dev)
+    if f.handle is not None:
+        f.handle.arrival_counts(f.d_p0.data_ptr(), f.d_depths.data_ptr(), R, cols, counts.data_ptr(), f.stream)
+    else:
+        z, p, d_x = f.upload_rows(rays.zs), f.upload_rows(rays.ps), f.upload_x()
+        _lib.arrival_counts_device(f.env, z.data_ptr(), p.data_ptr(), len(rays), S, d_x.data_ptr(), f.d_p0.data_ptr(),
+                                   f.d_depths.data_ptr(), R, cols, counts.data_ptr(), f.stream)
+    offsets = torch.zeros(R * n + 1, dtype=torch.int64, device=f.dev)
+    torch.cumsum(counts, 0, out=offsets[1:])
+    total = int(offsets[-1].item())
+    tube = torch.empty(total, dtype=torch.int32, device=f.dev)
+    w, T, P, I = (torch.empty(total, dtype=torch.float64, device=f.dev) for _ in range(4))
+    if total:
+        ptrs = (offsets.data_ptr(), total, tube.data_ptr(), w.data_ptr(), T.data_ptr(), P.data_ptr(), I.data_ptr())
+        if f.handle is not None:
+            f.handle.arrivals(f.d_p0.data_ptr(), f.d_depths.data_ptr(), R, cols, *ptrs, f.stream)
+        else:
+            t = f.upload_rows(rays.ts)
+            _lib.arrivals_device(f.env, t.data_ptr(), z.data_ptr(), p.data_ptr(), len(rays), S, d_x.data_ptr(),
+                                 f.d_p0.data_ptr(), f.d_depths.data_ptr(), R, cols, *ptrs, f.stream)
+    cin, rin, zin = f.tables
+    xs = f.xf[cols]
+    c_rx = _bilinear(np.broadcast_to(xs[None, :], (R, n)), np.broadcast_to(f.depths[:, None], (R, n)), rin, zin, cin)
+    return Arrivals(offsets.cpu().numpy(), f.depths, np.asarray(f.x)[cols], cols.astype(np.int64), tube.cpu().numpy(),
+                    w.cpu().numpy(), T.cpu().numpy(), P.cpu().numpy(), I.cpu().numpy(), np.asarray(rays.thetas, dtype=float),
+                    c_rx)
+
+
+__all__ = ["arrivals", "Arrivals"]

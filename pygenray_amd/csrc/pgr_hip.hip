@@ -53,3 +53,4 @@
 #include "pgr_eigen_hist.h"     // pgr_eigen_refine*, pgr_arrival_histogram_device
 #include "pgr_debug_entry.h"    // pgr_debug_math / pgr_debug_step / pgr_eval_points
 #include "pgr_tl.h"             // ray-tube intensity / transmission loss: pgr_fan_intensity, pgr_intensity_device
+#include "pgr_arrivals.h"       // ray-tube arrivals at receiver depths: pgr_fan_arrival_counts, pgr_fan_arrivals, ..._device

@@ -22,6 +22,7 @@
 struct TlArgs {
     const double* Z;          // depth samples, stored convention (depth = zsign * Z)
     const double* P;
+    const double* T;          // travel times (arrivals only; NULL for TL)
     const int* keep;          // column of surviving ray m in Z / P (NULL: m itself)
     int64_t N;                // rays held in Z / P (the column stride)
     int64_t M;                // surviving rays (tubes: M - 1)
@@ -33,7 +34,9 @@ struct TlArgs {
     const double* depths;     // [R]
     int64_t R;
     int64_t nchunk;
-    double* bounds;           // [S][nchunk][2]
+    const int32_t* cols;      // the columns walked: slot c is column cols[c] (NULL: slot s is column s, all S of them)
+    int32_t ncol;             // slots (S when cols is NULL)
+    double* bounds;           // [ncol][nchunk][2]
     double* out;              // [R][S]
 };
 
@@ -41,6 +44,8 @@ __device__ __forceinline__ int64_t tl_index(const TlArgs& a, int s, int64_t n)
 {
     return a.blocked ? (((int64_t)(s >> 2) * a.N + n) << 2) + (s & 3) : (int64_t)s * a.N + n;
 }
+
+__device__ __forceinline__ int tl_column(const TlArgs& a, int c) { return a.cols ? a.cols[c] : c; }
 
 __device__ __forceinline__ double tl_wave_min(double v)
 {
@@ -54,10 +59,11 @@ __device__ __forceinline__ double tl_wave_max(double v)
     return v;
 }
 
-// pass 1: [min, max] depth of the rays of chunk c (NaN samples ignored; an all-NaN chunk gets the empty [+inf, -inf])
+// pass 1: [min, max] depth of the rays of chunk c in column slot y (NaN samples ignored; an all-NaN chunk gets the empty
+// [+inf, -inf])
 __global__ void __launch_bounds__(256) pgr_tl_bounds(TlArgs a)
 {
-    const int s = blockIdx.y;
+    const int s = tl_column(a, blockIdx.y);
     const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int t = threadIdx.x & 63;
     if (c >= a.nchunk) return;                      // (whole waves: c is uniform in the wave)
@@ -71,16 +77,89 @@ __global__ void __launch_bounds__(256) pgr_tl_bounds(TlArgs a)
     lo = tl_wave_min(lo);
     hi = tl_wave_max(hi);
     if (t == 0) {
-        double* b = a.bounds + 2 * ((int64_t)s * a.nchunk + c);
+        double* b = a.bounds + 2 * ((int64_t)blockIdx.y * a.nchunk + c);
         b[0] = lo;
         b[1] = hi;
+    }
+}
+
+// the LDS of one wave's walk: the current chunk's tubes, and with RAYS its rays' depth, travel time and stored-sign slowness
+struct TlTubes { double lo[64], hi[64], I[64]; };
+struct TlRays { double d[64], T[64], p[64]; };
+
+// The tubes of chunk c in column s into LDS: lane t loads ray m = c * TL_TUBES + t (its depth, g and launch slowness),
+// takes its neighbour's by a lane shuffle and forms tube t (an empty interval [0, 0) where the tube adds nothing).  TL and
+// the arrival passes all form their tubes here, so they see the same tubes and the same bits of I.
+template <bool RAYS>
+__device__ __forceinline__ void tl_chunk_tubes(const TlArgs& a, const Ctx<false, 0>& C, int s, double x, double r,
+                                               int64_t c, int t, TlTubes& L, TlRays* Y)
+{
+    const int64_t m = c * TL_TUBES + t;
+    double dz = NAN, g = NAN, q0 = NAN, p = NAN, T = NAN;
+    if (m < a.M) {
+        const int64_t n = a.keep ? (int64_t)a.keep[m] : m;
+        const int64_t i = tl_index(a, s, n);
+        dz = a.zsign * a.Z[i];
+        p = a.P[i];
+        if (RAYS) T = a.T[i];
+        q0 = a.p0[m];
+        if (dz == dz && p == p) {
+            double cv, cp;
+            C.lookup(x, dz, cv, cp);
+            const double pc = p * cv;
+            if (fabs(pc) < 1.0) g = fdiv(cv, fsqrt(1.0 - pc * pc));
+        }
+    }
+    const double dz1 = __shfl_down(dz, 1), g1 = __shfl_down(g, 1), q1 = __shfl_down(q0, 1);
+    double lo = 0.0, hi = 0.0, I = 0.0;
+    if (t < TL_TUBES && m + 1 < a.M && g == g && g1 == g1 && dz != dz1) {
+        lo = fmin(dz, dz1);
+        hi = fmax(dz, dz1);
+        I = fdiv(0.5 * (g + g1) * fabs(q1 - q0), r * fabs(dz1 - dz));
+    }
+    __syncthreads();                               // (the previous chunk's tubes have been read)
+    L.lo[t] = lo;
+    L.hi[t] = hi;
+    L.I[t] = I;
+    if (RAYS) {
+        Y->d[t] = dz;
+        Y->T[t] = T;
+        Y->p[t] = -a.zsign * p;                    // RayFan.ps's sign whatever the fan kernel stored
+    }
+    __syncthreads();
+}
+
+// The walk of one wave over column s for its band of receivers (lane t: receiver depth d): the chunks of the column in
+// order, those whose interval misses the band skipped, and for every tube u of a chunk, in order, that holds d,
+// visit(u).  The tubes of chunk c are then in L (and Y), tube u being rays c * TL_TUBES + u and + u + 1.
+template <bool RAYS, typename Visit>
+__device__ __forceinline__ void tl_walk(const TlArgs& a, const Ctx<false, 0>& C, int slot, int s, double x, double r,
+                                        double d, int t, TlTubes& L, TlRays* Y, Visit visit)
+{
+    // the band's depth span (whatever the order of the depths)
+    const double dlo = tl_wave_min(d), dhi = tl_wave_max(d);
+    const double* bnd = a.bounds + 2 * (int64_t)slot * a.nchunk;
+    for (int64_t c0 = 0; c0 < a.nchunk; c0 += 64) {
+        bool hit = false;
+        if (c0 + t < a.nchunk) {
+            const double clo = bnd[2 * (c0 + t)], chi = bnd[2 * (c0 + t) + 1];
+            hit = (clo <= dhi) & (chi > dlo);      // a tube [lo, hi) of the chunk may hold a receiver of the band
+        }
+        unsigned long long mask = ballot64(hit);
+        while (mask) {
+            const int64_t c = c0 + __builtin_ctzll(mask);
+            mask &= mask - 1;
+            tl_chunk_tubes<RAYS>(a, C, s, x, r, c, t, L, Y);
+            for (int u = 0; u < TL_TUBES; u++)
+                if ((L.lo[u] <= d) & (d < L.hi[u])) visit(c, u);
+        }
     }
 }
 
 // pass 2: one wave per (column, band of 64 receivers)
 __global__ void __launch_bounds__(64) pgr_tl_sum(EnvDev env, TlArgs a)
 {
-    __shared__ double t_lo[64], t_hi[64], t_I[64];
+    __shared__ TlTubes L;
     const int s = blockIdx.x;
     const int t = threadIdx.x;
     const int64_t j = (int64_t)blockIdx.y * 64 + t;
@@ -92,69 +171,36 @@ __global__ void __launch_bounds__(64) pgr_tl_sum(EnvDev env, TlArgs a)
         if (rcv) a.out[j * a.S + s] = NAN;
         return;
     }
-    // the band's depth span (whatever the order of the depths)
-    const double dlo = tl_wave_min(d), dhi = tl_wave_max(d);
     const Ctx<false, 0> C(env, nullptr);
-    const double* bnd = a.bounds + 2 * (int64_t)s * a.nchunk;
     double acc = 0.0;
-    for (int64_t c0 = 0; c0 < a.nchunk; c0 += 64) {
-        bool hit = false;
-        if (c0 + t < a.nchunk) {
-            const double clo = bnd[2 * (c0 + t)], chi = bnd[2 * (c0 + t) + 1];
-            hit = (clo <= dhi) & (chi > dlo);      // a tube [lo, hi) of the chunk may hold a receiver of the band
-        }
-        unsigned long long mask = ballot64(hit);
-        while (mask) {
-            const int64_t c = c0 + __builtin_ctzll(mask);
-            mask &= mask - 1;
-            // lane t: ray m of the chunk, its depth, g and launch slowness
-            const int64_t m = c * TL_TUBES + t;
-            double dz = NAN, g = NAN, q0 = NAN;
-            if (m < a.M) {
-                const int64_t n = a.keep ? (int64_t)a.keep[m] : m;
-                const int64_t i = tl_index(a, s, n);
-                dz = a.zsign * a.Z[i];
-                const double p = a.P[i];
-                q0 = a.p0[m];
-                if (dz == dz && p == p) {
-                    double cv, cp;
-                    C.lookup(x, dz, cv, cp);
-                    const double pc = p * cv;
-                    if (fabs(pc) < 1.0) g = fdiv(cv, fsqrt(1.0 - pc * pc));
-                }
-            }
-            const double dz1 = __shfl_down(dz, 1), g1 = __shfl_down(g, 1), q1 = __shfl_down(q0, 1);
-            // tube (ray t, ray t + 1); an empty interval where the tube adds nothing
-            double lo = 0.0, hi = 0.0, I = 0.0;
-            if (t < TL_TUBES && m + 1 < a.M && g == g && g1 == g1 && dz != dz1) {
-                lo = fmin(dz, dz1);
-                hi = fmax(dz, dz1);
-                I = fdiv(0.5 * (g + g1) * fabs(q1 - q0), r * fabs(dz1 - dz));
-            }
-            __syncthreads();                       // (the previous chunk's tubes have been read)
-            t_lo[t] = lo;
-            t_hi[t] = hi;
-            t_I[t] = I;
-            __syncthreads();
-            for (int u = 0; u < TL_TUBES; u++)
-                if ((t_lo[u] <= d) & (d < t_hi[u])) acc = acc + t_I[u];
-        }
-    }
+    tl_walk<false>(a, C, s, s, x, r, d, t, L, nullptr, [&](int64_t, int u) { acc = acc + L.I[u]; });
     if (rcv) a.out[j * a.S + s] = acc;
 }
 
-// both passes on `stream`; the chunk bounds live in a stream-ordered allocation freed behind the second pass
-static int tl_run(const pgr_env* env, TlArgs a, hipStream_t st, const char* who)
+// pass 1 over a.ncol column slots (a.cols: HOST [ncol], uploaded here; NULL: all S columns), then `second` on `stream`; the
+// chunk bounds (and the column list) live in a stream-ordered allocation freed behind the second pass
+template <typename Second>
+static int tl_run(TlArgs a, const int32_t* cols, hipStream_t st, const char* who, Second second)
 {
     a.nchunk = (a.M - 1 + TL_TUBES - 1) / TL_TUBES;
+    if (!cols) a.ncol = a.S;
+    const size_t nb = (size_t)a.ncol * (size_t)a.nchunk * 16;
     void* b = nullptr;
-    if (hipMallocAsync(&b, (size_t)a.S * (size_t)a.nchunk * 16, st) != hipSuccess)
+    if (hipMallocAsync(&b, nb + (cols ? (size_t)a.ncol * sizeof(int32_t) : 0), st) != hipSuccess)
         return fail(std::string(who) + ": device allocation of the chunk bounds failed");
     a.bounds = (double*)b;
-    hipLaunchKernelGGL(pgr_tl_bounds, dim3((unsigned)((a.nchunk + 3) / 4), (unsigned)a.S), dim3(256), 0, st, a);
-    hipError_t e = hipGetLastError();
+    a.cols = nullptr;
+    hipError_t e = hipSuccess;
+    if (cols) {
+        a.cols = (const int32_t*)((char*)b + nb);
+        e = hipMemcpyAsync((void*)a.cols, cols, (size_t)a.ncol * sizeof(int32_t), hipMemcpyHostToDevice, st);
+    }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(pgr_tl_sum, dim3((unsigned)a.S, (unsigned)((a.R + 63) / 64)), dim3(64), 0, st, env->d, a);
+        hipLaunchKernelGGL(pgr_tl_bounds, dim3((unsigned)((a.nchunk + 3) / 4), (unsigned)a.ncol), dim3(256), 0, st, a);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) {
+        second(a);
         e = hipGetLastError();
     }
     (void)hipFreeAsync(b, st);
@@ -162,7 +208,14 @@ static int tl_run(const pgr_env* env, TlArgs a, hipStream_t st, const char* who)
     return 0;
 }
 
-static int tl_check(int64_t M, int32_t S, const double* p0, const double* depths, int64_t R, double* out, const char* who)
+static int tl_run(const pgr_env* env, TlArgs a, hipStream_t st, const char* who)
+{
+    return tl_run(a, nullptr, st, who, [&](const TlArgs& b) {
+        hipLaunchKernelGGL(pgr_tl_sum, dim3((unsigned)b.S, (unsigned)((b.R + 63) / 64)), dim3(64), 0, st, env->d, b);
+    });
+}
+
+static int tl_check(int64_t M, int32_t S, const double* p0, const double* depths, int64_t R, const void* out, const char* who)
 {
     if (!p0 || !depths || !out) return fail(std::string(who) + ": null argument");
     if (M < 2) return fail(std::string(who) + ": need at least two rays (one ray tube)");
@@ -172,22 +225,21 @@ static int tl_check(int64_t M, int32_t S, const double* p0, const double* depths
     return 0;
 }
 
-extern "C" int pgr_fan_intensity(pgr_fan* f, const double* p0, const double* depths, int64_t n_depths, double* out,
-                                 void* stream)
+// a device-resident fan's TlArgs: waits for its kernel, runs the caller's argument `check` (the fan's M is known then),
+// uploads the keep list and the save ranges on first use (held by the handle); the caller holds f->m
+template <typename Check>
+static int tl_fan_args(pgr_fan* f, TlArgs& a, const char* who, Check check)
 {
-    if (!f) return fail("pgr_fan_intensity: null fan");
-    if (!f->save) return fail("pgr_fan_intensity: the fan was launched without trajectories (S = 0)");
-    std::lock_guard<std::mutex> lock(f->m);
     HIPCHK(hipSetDevice(f->env->device));
     int rc = fan_finish(f);
     if (rc) return rc;
-    rc = tl_check(f->M, f->S, p0, depths, n_depths, out, "pgr_fan_intensity");
+    rc = check();
     if (rc) return rc;
     if (f->M != f->N && !f->d_keep) {
         // the columns of the surviving rays, uploaded once per fan (freed with it): dropped rays are skipped in place
         if (hipMalloc(&f->d_keep, (size_t)f->M * sizeof(int)) != hipSuccess) {
             f->d_keep = nullptr;
-            return fail("pgr_fan_intensity: device allocation failed");
+            return fail(std::string(who) + ": device allocation failed");
         }
         HIPCHK(hipMemcpy(f->d_keep, f->keep.data(), (size_t)f->M * sizeof(int), hipMemcpyHostToDevice));
     }
@@ -198,11 +250,25 @@ extern "C" int pgr_fan_intensity(pgr_fan* f, const double* p0, const double* dep
         HIPCHK(hipMemcpy(f->d.r, r.data(), (size_t)f->S * sizeof(double), hipMemcpyHostToDevice));
         f->r_filled = true;
     }
-    TlArgs a{};
-    a.Z = f->d.Z; a.P = f->d.P; a.keep = (f->M != f->N) ? f->d_keep : nullptr;
+    a = TlArgs{};
+    a.Z = f->d.Z; a.P = f->d.P; a.T = f->d.T; a.keep = (f->M != f->N) ? f->d_keep : nullptr;
     a.N = f->N; a.M = f->M; a.S = f->S; a.blocked = f->blocked ? 1 : 0;
     a.zsign = (f->flags & PGR_STORED_SIGN) ? -1.0 : 1.0;
-    a.x = f->d.r; a.p0 = p0; a.depths = depths; a.R = n_depths; a.out = out;
+    a.x = f->d.r;
+    return 0;
+}
+
+extern "C" int pgr_fan_intensity(pgr_fan* f, const double* p0, const double* depths, int64_t n_depths, double* out,
+                                 void* stream)
+{
+    if (!f) return fail("pgr_fan_intensity: null fan");
+    if (!f->save) return fail("pgr_fan_intensity: the fan was launched without trajectories (S = 0)");
+    std::lock_guard<std::mutex> lock(f->m);
+    TlArgs a;
+    int rc = tl_fan_args(f, a, "pgr_fan_intensity",
+                         [&] { return tl_check(f->M, f->S, p0, depths, n_depths, out, "pgr_fan_intensity"); });
+    if (rc) return rc;
+    a.p0 = p0; a.depths = depths; a.R = n_depths; a.out = out;
     return tl_run(f->env, a, (hipStream_t)stream, "pgr_fan_intensity");
 }
 
