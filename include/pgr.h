@@ -300,6 +300,29 @@ int pgr_arrivals_device(pgr_env* env, const double* T, const double* z, const do
                         const int32_t* cols, int32_t n_cols, const int64_t* offsets, int64_t n_arrivals, int32_t* tube,
                         double* w, double* T_out, double* p_out, double* I, void* stream);
 
+/* Incoherent geometric Gaussian-beam intensity of a fan on a range-depth grid ("Gaussian beams"): the tubes of
+ * pgr_fan_intensity, each spread over depth as a Gaussian instead of a top hat.  At save sample s, tube k (rays k, k + 1)
+ * with both g finite (no NaN sample, |p c| < 1 at both ends; equal depths allowed) has
+ *   E_k = 0.5 (g_k + g_k+1) |p0_k+1 - p0_k| / r_s,   m_k = 0.5 (d_k + d_k+1),   A_k = E_k / (sigma_k sqrt(2 pi)),
+ *   sigma_k = max(D_k-1, D_k, D_k+1, min_width),   D_i = |d_i+1 - d_i|   (NaN widths and those past the fan's ends ignored),
+ * and out[j * S + s] (DEVICE, [n_depths][S], overwritten) = the sum, in increasing k from 0.0 and for each tube over the
+ * centres m_k, -m_k and 2 bottom[s] - m_k in that order (the beam and its images in the surface and the bottom), of
+ *   A_k exp(-v / 2),   v = ((depths[j] - centre) / sigma_k)^2,   over the terms with v <= 16 (beams cut at 4 sigma).
+ * exp is a fixed sequence of + - x, rint and ldexp (the library's own, within 1.5 ulp on [-8, 0]).  A receiver no beam
+ * reaches gets 0; the column r_s == 0 is NaN.  Deterministic: no atomics, every receiver's sum is formed in order by one
+ * lane, so repeated calls are bit-equal and equal the sequential sum.  TL = -10 log10(out).
+ *
+ * bottom[S] (DEVICE): the bottom depth at each save range, in the frame the fan was traced in (flat-earth, mirrored for a
+ * backwards fan).  min_width: the floor on sigma, metres, finite and > 0.
+ * pgr_fan_beam_intensity: a device-resident fan, with the fan arguments, waiting and streams of pgr_fan_intensity.
+ * pgr_beam_intensity_device: caller buffers z, p (DEVICE) [n_samples][n_rays] rows, stored sign convention, and x as
+ * pgr_intensity_device. */
+int pgr_fan_beam_intensity(pgr_fan* fan, const double* p0, const double* bottom, const double* depths, int64_t n_depths,
+                           double min_width, double* out, void* stream);
+int pgr_beam_intensity_device(pgr_env* env, const double* z, const double* p, int64_t n_rays, int32_t n_samples,
+                              const double* x, const double* p0, const double* bottom, const double* depths,
+                              int64_t n_depths, double min_width, double* out, void* stream);
+
 /* Tuning options of ONE environment (per-ray results never depend on them; there is no process-wide
  * state: host threads that drive different GPUs hold different environments).
  *   PGR_OPT_WAVES_PER_BLOCK  a = waves (of 64 rays) per workgroup, 0 = automatic

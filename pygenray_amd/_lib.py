@@ -522,6 +522,15 @@ class FanHandle:
         L.pgr_fan_intensity.argtypes = [_vp, _vp, _vp, _i64, _vp, _vp]
         check(L.pgr_fan_intensity(self._h, _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vp(out_ptr), _vp(stream or None)))
 
+    def beam_intensity(self, p0_ptr, bottom_ptr, depths_ptr, n_depths, min_width, out_ptr, stream=0):
+        """pgr_fan_beam_intensity on raw device pointers (ints): out[n_depths][S] = the Gaussian-beam intensity of this fan's
+        surviving rays at the receiver depths, bottom[S] the bottom depth at each save range (include/pgr.h)."""
+        L = load()
+        L.pgr_fan_beam_intensity.restype = ctypes.c_int
+        L.pgr_fan_beam_intensity.argtypes = [_vp, _vp, _vp, _vp, _i64, ctypes.c_double, _vp, _vp]
+        check(L.pgr_fan_beam_intensity(self._h, _vp(p0_ptr), _vp(bottom_ptr), _vp(depths_ptr), int(n_depths),
+                                       float(min_width), _vp(out_ptr), _vp(stream or None)))
+
     def arrival_counts(self, p0_ptr, depths_ptr, n_depths, cols, counts_ptr, stream=0):
         """pgr_fan_arrival_counts: counts[n_depths][len(cols)] (int64, device pointer) = the arrivals of this fan's surviving
         rays at each receiver depth and requested column; `cols` is a host sequence of column indices (include/pgr.h)."""
@@ -641,6 +650,19 @@ def intensity_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, depths
     L.pgr_intensity_device.argtypes = [_vp, _vp, _vp, _i64, ctypes.c_int32, _vp, _vp, _vp, _i64, _vp, _vp]
     check(L.pgr_intensity_device(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples), _vp(x_ptr), _vp(p0_ptr),
                                  _vp(depths_ptr), int(n_depths), _vp(out_ptr), _vp(stream or None)))
+
+
+def beam_intensity_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, bottom_ptr, depths_ptr, n_depths, min_width,
+                          out_ptr, stream=0):
+    """pgr_beam_intensity_device on raw device pointers (ints): the Gaussian-beam intensity of caller buffers z / p
+    [n_samples][n_rays] (stored sign convention) on `env` (an EnvHandle); see include/pgr.h."""
+    L = load()
+    L.pgr_beam_intensity_device.restype = ctypes.c_int
+    L.pgr_beam_intensity_device.argtypes = [_vp, _vp, _vp, _i64, ctypes.c_int32, _vp, _vp, _vp, _vp, _i64, ctypes.c_double,
+                                            _vp, _vp]
+    check(L.pgr_beam_intensity_device(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples), _vp(x_ptr),
+                                      _vp(p0_ptr), _vp(bottom_ptr), _vp(depths_ptr), int(n_depths), float(min_width),
+                                      _vp(out_ptr), _vp(stream or None)))
 
 
 def arrival_counts_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, depths_ptr, n_depths, cols, counts_ptr,

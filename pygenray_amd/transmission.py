@@ -1,13 +1,16 @@
-"""``transmission_loss``: incoherent ray-tube transmission loss of a fan on a range-depth grid ("Transmission loss").
+"""Incoherent transmission loss of a fan on a range-depth grid: ``transmission_loss``, the ray-tube (top hat) sum (DESIGN.md,
+"Transmission loss"), and ``beam_transmission_loss``, the same tubes spread as geometric Gaussian beams (DESIGN.md,
+"Gaussian beams").
 
-No reference counterpart: pygenray gives back rays, not amplitudes.  The tube sum runs in HIP (csrc/pgr_tl.h) on the fan's
-trajectories where they already are -- in HBM for a device-resident fan, uploaded through torch for a host fan.  There is
-no CPU path.
+No reference counterpart: pygenray gives back rays, not amplitudes.  Both sums run in HIP (csrc/pgr_tl.h, csrc/pgr_beams.h)
+on the fan's trajectories where they already are -- in HBM for a device-resident fan, uploaded through torch for a host
+fan.  There is no CPU path.
 """
 import numpy as np
 
 from . import _lib
-from .host_physics import bilinear_interp
+from .environment import _mirror_envi_arrays, _unpack_envi
+from .host_physics import bilinear_interp, linear_interp
 from .launch_rays import _device_env, _initial_slowness
 
 _NO_FE_MSG = ("Flat earth transformation has not been applied. Set `flat_earth_transform=True` "
@@ -80,6 +83,14 @@ class _FanFrame:
         import torch
         return torch.from_numpy(np.ascontiguousarray(self.xf)).to(self.dev)
 
+    def bottom(self):
+        """The bottom depth at each save range in the frame the fan was traced in (flat-earth, mirrored for a backwards fan):
+        host_physics.linear_interp of the bathymetry at xf."""
+        cin, cpin, rin, _, depths, depth_ranges, angles = _unpack_envi(self.environment, flatearth=self.flatearth)
+        if self.backwards:
+            depths, depth_ranges = _mirror_envi_arrays(cin, cpin, rin, depths, depth_ranges, angles)[3:5]
+        return np.array([linear_interp(float(v), depth_ranges, depths) for v in self.xf])
+
 
 def transmission_loss(rays, receiver_depths, environment, flatearth=True, device=0, intensity=False):
     """Incoherent ray-tube transmission loss of ``rays`` (a ``RayFan`` from ``shoot_rays``) at ``receiver_depths`` (metres,
@@ -112,4 +123,49 @@ def transmission_loss(rays, receiver_depths, environment, flatearth=True, device
         return -10.0 * np.log10(I)
 
 
-__all__ = ["transmission_loss"]
+def beam_transmission_loss(rays, receiver_depths, environment, flatearth=True, device=0, intensity=False, min_width=10.0):
+    """Incoherent Gaussian-beam transmission loss of ``rays`` (a ``RayFan`` from ``shoot_rays``) at ``receiver_depths``
+    (metres, positive down, strictly ascending) on the fan's save ranges -> ndarray ``(len(receiver_depths), S)``:
+    ``-10 log10(I)`` dB re 1 m (``+inf`` where no beam reaches, NaN in the source's own column), or ``I`` itself with
+    ``intensity=True``.  The ray tubes of ``transmission_loss``, each spread over depth as a geometric Gaussian beam instead
+    of a top hat (as in Bellhop): tube k (rays k, k + 1) carries
+
+        E_k = 0.5 (g_k + g_k+1) |p0_k+1 - p0_k| / r,   g = c / sqrt(1 - (p c)^2)
+
+    (transmission_loss's I times the tube's depth extent) in a Gaussian of centre m_k = (d_k + d_k+1) / 2 and width
+    sigma_k = max(|Δd_k-1|, |Δd_k|, |Δd_k+1|, min_width) -- the widest of the tube and its two neighbours, so that a tube
+    folded at a reflection spreads a full tube's energy over a full tube's width -- and
+
+        I(d) = sum_k  A_k [G(d - m_k) + G(d + m_k) + G(d - 2 b + m_k)],   A_k = E_k / (sigma_k sqrt(2 pi)),
+        G(e) = exp(-e^2 / (2 sigma_k^2)) for |e| <= 4 sigma_k, else 0,
+
+    summed tube by tube in launch order: the beam and its images in the surface and in the bottom b (the bathymetry at each
+    save range), which fold the energy that would leave the water column back into it.  Beams are cut at 4 sigma (the mass
+    lost, 1 - erf(2 sqrt 2) = 6.3e-5, is 2.8e-4 dB).  ``min_width`` (metres, > 0) is a floor on the beam width: about a
+    wavelength c / f.  Incoherent, perfect boundary reflection; the sound speed and bathymetry are those of the environment
+    the fan was traced in (``environment`` with ``flatearth``; the mirrored frame of a backwards fan).  Unlike the top hat,
+    no spikes at caustics and no strip along the boundaries; receivers outside [0, b] get what the formula gives.  A
+    device-resident fan is processed where it is and stays device resident."""
+    w = float(min_width)
+    if not (np.isfinite(w) and w > 0):
+        raise ValueError("min_width must be finite and > 0")
+    f = _FanFrame(rays, receiver_depths, environment, flatearth, "beam_transmission_loss").to_device(device)
+    import torch
+
+    R, S = len(f.depths), len(f.x)
+    out = torch.empty((R, S), dtype=torch.float64, device=f.dev)
+    d_b = torch.from_numpy(f.bottom()).to(f.dev)
+    if f.handle is not None:
+        f.handle.beam_intensity(f.d_p0.data_ptr(), d_b.data_ptr(), f.d_depths.data_ptr(), R, w, out.data_ptr(), f.stream)
+    else:
+        z, p, d_x = f.upload_rows(rays.zs), f.upload_rows(rays.ps), f.upload_x()
+        _lib.beam_intensity_device(f.env, z.data_ptr(), p.data_ptr(), len(rays), S, d_x.data_ptr(), f.d_p0.data_ptr(),
+                                   d_b.data_ptr(), f.d_depths.data_ptr(), R, w, out.data_ptr(), f.stream)
+    I = out.cpu().numpy()
+    if intensity:
+        return I
+    with np.errstate(divide="ignore"):
+        return -10.0 * np.log10(I)
+
+
+__all__ = ["transmission_loss", "beam_transmission_loss"]
