@@ -233,6 +233,19 @@ def load():
     L.pgr_env_set_option.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     L.pgr_eval_points.restype = ctypes.c_int
     L.pgr_eval_points.argtypes = [_vp, _dp, _dp, _i64, _dp]
+    # the ray-tube entries (csrc/pgr_tl.h, pgr_arrivals.h, pgr_beams.h): on a fan handle, then on caller buffers
+    i32, f64 = ctypes.c_int32, ctypes.c_double
+    for name, argtypes in (
+            ("pgr_fan_intensity", [_vp, _vp, _vp, _i64, _vp, _vp]),
+            ("pgr_fan_beam_intensity", [_vp, _vp, _vp, _vp, _i64, f64, _vp, _vp]),
+            ("pgr_fan_arrival_counts", [_vp, _vp, _vp, _i64, _vp, i32, _vp, _vp]),
+            ("pgr_fan_arrivals", [_vp, _vp, _vp, _i64, _vp, i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+            ("pgr_intensity_device", [_vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _i64, _vp, _vp]),
+            ("pgr_beam_intensity_device", [_vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _vp, _i64, f64, _vp, _vp]),
+            ("pgr_arrival_counts_device", [_vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _i64, _vp, i32, _vp, _vp]),
+            ("pgr_arrivals_device", [_vp, _vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _i64, _vp, i32, _vp, _i64] + [_vp] * 6)):
+        getattr(L, name).restype = ctypes.c_int
+        getattr(L, name).argtypes = argtypes
     _lib = L
     return L
 
@@ -517,41 +530,30 @@ class FanHandle:
     def intensity(self, p0_ptr, depths_ptr, n_depths, out_ptr, stream=0):
         """pgr_fan_intensity on raw device pointers (ints): out[n_depths][S] = the ray-tube intensity of this fan's surviving
         rays at the receiver depths (include/pgr.h); p0 holds the M surviving rays' launch slowness.  Enqueued on `stream`."""
-        L = load()
-        L.pgr_fan_intensity.restype = ctypes.c_int
-        L.pgr_fan_intensity.argtypes = [_vp, _vp, _vp, _i64, _vp, _vp]
-        check(L.pgr_fan_intensity(self._h, _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vp(out_ptr), _vp(stream or None)))
+        check(load().pgr_fan_intensity(self._h, _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vp(out_ptr),
+                                       _vp(stream or None)))
 
     def beam_intensity(self, p0_ptr, bottom_ptr, depths_ptr, n_depths, min_width, out_ptr, stream=0):
         """pgr_fan_beam_intensity on raw device pointers (ints): out[n_depths][S] = the Gaussian-beam intensity of this fan's
         surviving rays at the receiver depths, bottom[S] the bottom depth at each save range (include/pgr.h)."""
-        L = load()
-        L.pgr_fan_beam_intensity.restype = ctypes.c_int
-        L.pgr_fan_beam_intensity.argtypes = [_vp, _vp, _vp, _vp, _i64, ctypes.c_double, _vp, _vp]
-        check(L.pgr_fan_beam_intensity(self._h, _vp(p0_ptr), _vp(bottom_ptr), _vp(depths_ptr), int(n_depths),
-                                       float(min_width), _vp(out_ptr), _vp(stream or None)))
+        check(load().pgr_fan_beam_intensity(self._h, _vp(p0_ptr), _vp(bottom_ptr), _vp(depths_ptr), int(n_depths),
+                                            float(min_width), _vp(out_ptr), _vp(stream or None)))
 
     def arrival_counts(self, p0_ptr, depths_ptr, n_depths, cols, counts_ptr, stream=0):
         """pgr_fan_arrival_counts: counts[n_depths][len(cols)] (int64, device pointer) = the arrivals of this fan's surviving
         rays at each receiver depth and requested column; `cols` is a host sequence of column indices (include/pgr.h)."""
-        L = load()
-        L.pgr_fan_arrival_counts.restype = ctypes.c_int
-        L.pgr_fan_arrival_counts.argtypes = [_vp, _vp, _vp, _i64, _vp, ctypes.c_int32, _vp, _vp]
         c = np.ascontiguousarray(cols, dtype=np.int32)
-        check(L.pgr_fan_arrival_counts(self._h, _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vptr(c), len(c),
-                                       _vp(counts_ptr), _vp(stream or None)))
+        check(load().pgr_fan_arrival_counts(self._h, _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vptr(c), len(c),
+                                            _vp(counts_ptr), _vp(stream or None)))
 
     def arrivals(self, p0_ptr, depths_ptr, n_depths, cols, offsets_ptr, n_arrivals, tube_ptr, w_ptr, t_ptr, p_ptr, i_ptr,
                  stream=0):
         """pgr_fan_arrivals: the arrivals themselves, written from offsets[j * len(cols) + c] into tube (int32) / w / T / p /
         I (device pointers holding n_arrivals each)."""
-        L = load()
-        L.pgr_fan_arrivals.restype = ctypes.c_int
-        L.pgr_fan_arrivals.argtypes = [_vp, _vp, _vp, _i64, _vp, ctypes.c_int32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]
         c = np.ascontiguousarray(cols, dtype=np.int32)
-        check(L.pgr_fan_arrivals(self._h, _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vptr(c), len(c), _vp(offsets_ptr),
-                                 int(n_arrivals), _vp(tube_ptr), _vp(w_ptr), _vp(t_ptr), _vp(p_ptr), _vp(i_ptr),
-                                 _vp(stream or None)))
+        check(load().pgr_fan_arrivals(self._h, _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vptr(c), len(c),
+                                      _vp(offsets_ptr), int(n_arrivals), _vp(tube_ptr), _vp(w_ptr), _vp(t_ptr), _vp(p_ptr),
+                                      _vp(i_ptr), _vp(stream or None)))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -645,50 +647,35 @@ def arrival_histogram_device(device, t_ptr, t_stride, status_ptr, status_stride,
 def intensity_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, depths_ptr, n_depths, out_ptr, stream=0):
     """pgr_intensity_device on raw device pointers (ints): the ray-tube intensity of caller buffers z / p [n_samples][n_rays]
     (stored sign convention) on `env` (an EnvHandle); see include/pgr.h."""
-    L = load()
-    L.pgr_intensity_device.restype = ctypes.c_int
-    L.pgr_intensity_device.argtypes = [_vp, _vp, _vp, _i64, ctypes.c_int32, _vp, _vp, _vp, _i64, _vp, _vp]
-    check(L.pgr_intensity_device(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples), _vp(x_ptr), _vp(p0_ptr),
-                                 _vp(depths_ptr), int(n_depths), _vp(out_ptr), _vp(stream or None)))
+    check(load().pgr_intensity_device(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples), _vp(x_ptr),
+                                      _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vp(out_ptr), _vp(stream or None)))
 
 
 def beam_intensity_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, bottom_ptr, depths_ptr, n_depths, min_width,
                           out_ptr, stream=0):
     """pgr_beam_intensity_device on raw device pointers (ints): the Gaussian-beam intensity of caller buffers z / p
     [n_samples][n_rays] (stored sign convention) on `env` (an EnvHandle); see include/pgr.h."""
-    L = load()
-    L.pgr_beam_intensity_device.restype = ctypes.c_int
-    L.pgr_beam_intensity_device.argtypes = [_vp, _vp, _vp, _i64, ctypes.c_int32, _vp, _vp, _vp, _vp, _i64, ctypes.c_double,
-                                            _vp, _vp]
-    check(L.pgr_beam_intensity_device(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples), _vp(x_ptr),
-                                      _vp(p0_ptr), _vp(bottom_ptr), _vp(depths_ptr), int(n_depths), float(min_width),
-                                      _vp(out_ptr), _vp(stream or None)))
+    check(load().pgr_beam_intensity_device(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples), _vp(x_ptr),
+                                           _vp(p0_ptr), _vp(bottom_ptr), _vp(depths_ptr), int(n_depths), float(min_width),
+                                           _vp(out_ptr), _vp(stream or None)))
 
 
 def arrival_counts_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, depths_ptr, n_depths, cols, counts_ptr,
                           stream=0):
     """pgr_arrival_counts_device on raw device pointers (ints) of caller buffers z / p [n_samples][n_rays] (stored sign
     convention) on `env` (an EnvHandle); `cols` a host sequence of column indices; see include/pgr.h."""
-    L = load()
-    L.pgr_arrival_counts_device.restype = ctypes.c_int
-    L.pgr_arrival_counts_device.argtypes = [_vp, _vp, _vp, _i64, ctypes.c_int32, _vp, _vp, _vp, _i64, _vp, ctypes.c_int32,
-                                            _vp, _vp]
     c = np.ascontiguousarray(cols, dtype=np.int32)
-    check(L.pgr_arrival_counts_device(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples), _vp(x_ptr),
-                                      _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vptr(c), len(c), _vp(counts_ptr),
-                                      _vp(stream or None)))
+    check(load().pgr_arrival_counts_device(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples), _vp(x_ptr),
+                                           _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vptr(c), len(c), _vp(counts_ptr),
+                                           _vp(stream or None)))
 
 
 def arrivals_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, depths_ptr, n_depths, cols, offsets_ptr,
                     n_arrivals, tube_ptr, w_ptr, t_out_ptr, p_out_ptr, i_ptr, stream=0):
     """pgr_arrivals_device on raw device pointers (ints): arrival_counts_device's walk, writing the arrivals; see
     include/pgr.h."""
-    L = load()
-    L.pgr_arrivals_device.restype = ctypes.c_int
-    L.pgr_arrivals_device.argtypes = [_vp, _vp, _vp, _vp, _i64, ctypes.c_int32, _vp, _vp, _vp, _i64, _vp, ctypes.c_int32,
-                                      _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]
     c = np.ascontiguousarray(cols, dtype=np.int32)
-    check(L.pgr_arrivals_device(env._h, _vp(t_ptr), _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples), _vp(x_ptr),
-                                _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vptr(c), len(c), _vp(offsets_ptr),
-                                int(n_arrivals), _vp(tube_ptr), _vp(w_ptr), _vp(t_out_ptr), _vp(p_out_ptr), _vp(i_ptr),
-                                _vp(stream or None)))
+    check(load().pgr_arrivals_device(env._h, _vp(t_ptr), _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples),
+                                     _vp(x_ptr), _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vptr(c), len(c),
+                                     _vp(offsets_ptr), int(n_arrivals), _vp(tube_ptr), _vp(w_ptr), _vp(t_out_ptr),
+                                     _vp(p_out_ptr), _vp(i_ptr), _vp(stream or None)))

@@ -6,7 +6,6 @@ already are -- in HBM for a device-resident fan, uploaded through torch for a ho
 """
 import numpy as np
 
-from . import _lib
 from .transmission import _FanFrame
 
 
@@ -133,25 +132,15 @@ def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=N
 
     R, n = len(f.depths), len(cols)
     counts = torch.empty(R * n, dtype=torch.int64, device=f.dev)
-    if f.handle is not None:
-        f.handle.arrival_counts(f.d_p0.data_ptr(), f.d_depths.data_ptr(), R, cols, counts.data_ptr(), f.stream)
-    else:
-        z, p, d_x = f.upload_rows(rays.zs), f.upload_rows(rays.ps), f.upload_x()
-        _lib.arrival_counts_device(f.env, z.data_ptr(), p.data_ptr(), len(rays), S, d_x.data_ptr(), f.d_p0.data_ptr(),
-                                   f.d_depths.data_ptr(), R, cols, counts.data_ptr(), f.stream)
+    f.run("arrival_counts", f.d_depths.data_ptr(), R, cols, counts.data_ptr())
     offsets = torch.zeros(R * n + 1, dtype=torch.int64, device=f.dev)
     torch.cumsum(counts, 0, out=offsets[1:])
     total = int(offsets[-1].item())
     tube = torch.empty(total, dtype=torch.int32, device=f.dev)
     w, T, P, I = (torch.empty(total, dtype=torch.float64, device=f.dev) for _ in range(4))
     if total:
-        ptrs = (offsets.data_ptr(), total, tube.data_ptr(), w.data_ptr(), T.data_ptr(), P.data_ptr(), I.data_ptr())
-        if f.handle is not None:
-            f.handle.arrivals(f.d_p0.data_ptr(), f.d_depths.data_ptr(), R, cols, *ptrs, f.stream)
-        else:
-            t = f.upload_rows(rays.ts)
-            _lib.arrivals_device(f.env, t.data_ptr(), z.data_ptr(), p.data_ptr(), len(rays), S, d_x.data_ptr(),
-                                 f.d_p0.data_ptr(), f.d_depths.data_ptr(), R, cols, *ptrs, f.stream)
+        f.run("arrivals", f.d_depths.data_ptr(), R, cols, offsets.data_ptr(), total, tube.data_ptr(), w.data_ptr(),
+              T.data_ptr(), P.data_ptr(), I.data_ptr())
     cin, rin, zin = f.tables
     xs = f.xf[cols]
     c_rx = _bilinear(np.broadcast_to(xs[None, :], (R, n)), np.broadcast_to(f.depths[:, None], (R, n)), rin, zin, cin)

@@ -1,5 +1,6 @@
-// pgr_tl.h -- ray-tube intensity (transmission loss) of a fan on a range-depth grid: pgr_fan_intensity, pgr_intensity_device.
-// (Part of the ONE translation unit pgr_hip.hip, included there last; not a stand-alone header.)
+// pgr_tl.h -- the ray-tube walk of a fan's trajectories, shared by every product on the tubes, and on it the ray-tube
+// intensity (transmission loss) on a range-depth grid: pgr_fan_intensity, pgr_intensity_device.
+// (Part of the ONE translation unit pgr_hip.hip, included there after the fan side; not a stand-alone header.)
 //
 // The quantity (DESIGN.md section "Transmission loss"): adjacent surviving rays k, k + 1 bound a tube; at save sample s
 //   g = c / sqrt(1 - (p c)^2),   I_k(s) = 0.5 (g_k + g_k+1) |p0_k+1 - p0_k| / (r_s |z_k+1 - z_k|),   r_s = |x_s - x_0|,
@@ -7,13 +8,16 @@
 // depth of the tube's two samples).  A tube with a NaN sample, |p c| >= 1 at either end or z_k+1 == z_k adds nothing; the
 // column r_s == 0 is NaN.
 //
-// Two passes, no atomics:
-//   pgr_tl_bounds  one wave per (column s, chunk of TL_TUBES consecutive tubes = TL_TUBES + 1 rays): the chunk's depth interval;
-//   pgr_tl_sum     one wave per (column s, band of 64 receivers), a lane per receiver: walks the chunks of its column in
-//                  order, skips those whose interval misses the band, and for each of the others the lanes form the chunk's
-//                  tubes (lane t: ray t of the chunk, its neighbour by a lane shuffle) into LDS, then every lane adds, tube by
-//                  tube in order, those that contain its receiver.  Each receiver's sum is formed by one lane in tube order,
-//                  so the result does not depend on scheduling and equals the sequential sum bit for bit.
+// Two passes, no atomics, for every tube product (TL and the arrivals of pgr_arrivals.h on this file's tubes of 63, the
+// Gaussian beams of pgr_beams.h on tubes of 61 with a halo ray either side):
+//   pass 1  tube_bounds: one wave per (column slot, chunk of consecutive tubes): the depth interval the chunk's tubes can
+//           reach (TL: its rays' depths), into a.bounds;
+//   pass 2  tube_walk: one wave per (column slot, band of 64 receivers), a lane per receiver: walks the chunks of its column
+//           in order and skips those whose interval fails the product's test against the band; for each of the others the
+//           lanes form the chunk's tubes (lane t: ray t of the chunk, its neighbours by lane shuffles) into LDS, then every
+//           lane goes through them in order for its own receiver.  Each receiver's result is formed by one lane in tube
+//           order, so it does not depend on scheduling and equals the sequential sum bit for bit.
+// tube_run launches both on the caller's stream; tl_fan_entry and tl_buffer_entry are the prologues of the C entries.
 #ifndef PGR_TL_H
 #define PGR_TL_H
 
@@ -40,8 +44,10 @@ struct TlArgs {
     double* out;              // [R][S]
 };
 
-__device__ __forceinline__ int64_t tl_index(const TlArgs& a, int s, int64_t n)
+// where surviving ray m's sample s lies in Z / P (dropped rays skipped through the keep list)
+__device__ __forceinline__ int64_t tl_index(const TlArgs& a, int s, int64_t m)
 {
+    const int64_t n = a.keep ? (int64_t)a.keep[m] : m;
     return a.blocked ? (((int64_t)(s >> 2) * a.N + n) << 2) + (s & 3) : (int64_t)s * a.N + n;
 }
 
@@ -59,57 +65,129 @@ __device__ __forceinline__ double tl_wave_max(double v)
     return v;
 }
 
-// pass 1: [min, max] depth of the rays of chunk c in column slot y (NaN samples ignored; an all-NaN chunk gets the empty
-// [+inf, -inf])
-__global__ void __launch_bounds__(256) pgr_tl_bounds(TlArgs a)
+// Pass 1 of a tube shape (TUBES tubes per chunk, lane t holding ray c * TUBES + t + RAY0): one wave per (column slot
+// blockIdx.y, chunk c).  interval(t, m, lo, hi) sets the part of the chunk's interval lane t knows from its ray m; the
+// wave's [min lo, max hi] (none: the empty [+inf, -inf]) is the chunk's, with PAD widened by 2^-40 of its magnitude.
+template <int TUBES, int RAY0, bool PAD, typename Interval>
+__device__ __forceinline__ void tube_bounds(const TlArgs& a, Interval interval)
 {
-    const int s = tl_column(a, blockIdx.y);
     const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int t = threadIdx.x & 63;
     if (c >= a.nchunk) return;                      // (whole waves: c is uniform in the wave)
-    const int64_t m = c * TL_TUBES + t;
     double lo = INFINITY, hi = -INFINITY;
-    if (m < a.M) {
-        const int64_t n = a.keep ? (int64_t)a.keep[m] : m;
-        const double d = a.zsign * a.Z[tl_index(a, s, n)];
-        if (d == d) { lo = d; hi = d; }
-    }
+    interval(t, c * TUBES + t + RAY0, lo, hi);
     lo = tl_wave_min(lo);
     hi = tl_wave_max(hi);
     if (t == 0) {
+        if (PAD && lo <= hi) {
+            const double pad = 0x1p-40 * fmax(fabs(lo), fabs(hi));
+            lo -= pad;
+            hi += pad;
+        }
         double* b = a.bounds + 2 * ((int64_t)blockIdx.y * a.nchunk + c);
         b[0] = lo;
         b[1] = hi;
     }
 }
 
+// TL's pass 1: [min, max] depth of the rays of chunk c in column slot y (NaN samples ignored)
+__global__ void __launch_bounds__(256) pgr_tl_bounds(TlArgs a)
+{
+    const int s = tl_column(a, blockIdx.y);
+    tube_bounds<TL_TUBES, 0, false>(a, [&](int, int64_t m, double& lo, double& hi) {
+        if (m < a.M) {
+            const double d = a.zsign * a.Z[tl_index(a, s, m)];
+            if (d == d) { lo = d; hi = d; }
+        }
+    });
+}
+
+// The band of a pass-2 wave: column slot blockIdx.x (column s: a.cols[slot] with COLS, else the slot itself), lane t's
+// receiver j (rcv: j < R; the lanes past the last receiver take its depth, so the band's span is the receivers'), its
+// depth d, and the column's range x and distance r from the source (r == 0: the source's own column, uniform in the wave)
+struct TlBand {
+    int slot, s, t;
+    int64_t j;
+    bool rcv;
+    double d, x, r;
+    // an image's value at (j, s): a.out[R][S]
+    __device__ __forceinline__ void put(const TlArgs& a, double v) const { if (rcv) a.out[j * a.S + s] = v; }
+};
+
+template <bool COLS>
+__device__ __forceinline__ TlBand tl_band(const TlArgs& a)
+{
+    TlBand b;
+    b.slot = blockIdx.x;
+    b.s = COLS ? a.cols[b.slot] : b.slot;
+    b.t = threadIdx.x;
+    b.j = (int64_t)blockIdx.y * 64 + b.t;
+    b.rcv = b.j < a.R;
+    b.d = b.rcv ? a.depths[b.j] : a.depths[a.R - 1];
+    b.x = a.x[b.s];
+    b.r = fabs(b.x - a.x[0]);
+    return b;
+}
+
+// The walk of a pass-2 wave over column slot `slot` for its band (lane t: receiver depth d): the chunks of the column in
+// order, and for each whose interval [lo, hi] passes test(lo, hi, dlo, dhi) against the band's span -- a mask of BITS
+// tests, evaluated by the lane c mod 64 -- chunk(c, mask), uniformly in the wave (BITS = 1: the mask is 1).
+template <int BITS, typename Test, typename Chunk>
+__device__ __forceinline__ void tube_walk(const TlArgs& a, int slot, double d, int t, Test test, Chunk chunk)
+{
+    // the band's depth span (whatever the order of the depths)
+    const double dlo = tl_wave_min(d), dhi = tl_wave_max(d);
+    const double* bnd = a.bounds + 2 * (int64_t)slot * a.nchunk;
+    for (int64_t c0 = 0; c0 < a.nchunk; c0 += 64) {
+        int hit = 0;
+        if (c0 + t < a.nchunk) hit = test(bnd[2 * (c0 + t)], bnd[2 * (c0 + t) + 1], dlo, dhi);
+        unsigned long long mask = ballot64(hit != 0);
+        while (mask) {
+            const int l = __builtin_ctzll(mask);
+            mask &= mask - 1;
+            chunk(c0 + l, BITS == 1 ? 1 : __shfl(hit, l));
+        }
+    }
+}
+
+// Lane t's ray m of column s when `in`, else all NaN: its depth d, slowness p (stored sign), with RAYS its travel time T,
+// its launch slowness q0 and g = c / sqrt(1 - (p c)^2) (NaN for a NaN sample or |p c| >= 1).  Every tube shape loads its
+// rays here, so TL, the arrivals and the beams see the same bits of g.
+struct TlRay { double d, p, T, q0, g; };
+
+template <bool RAYS>
+__device__ __forceinline__ TlRay tl_ray(const TlArgs& a, const Ctx<false, 0>& C, int s, double x, int64_t m, bool in)
+{
+    TlRay y{NAN, NAN, NAN, NAN, NAN};
+    if (in) {
+        const int64_t i = tl_index(a, s, m);
+        y.d = a.zsign * a.Z[i];
+        y.p = a.P[i];
+        if (RAYS) y.T = a.T[i];
+        y.q0 = a.p0[m];
+        if (y.d == y.d && y.p == y.p) {
+            double cv, cp;
+            C.lookup(x, y.d, cv, cp);
+            const double pc = y.p * cv;
+            if (fabs(pc) < 1.0) y.g = fdiv(cv, fsqrt(1.0 - pc * pc));
+        }
+    }
+    return y;
+}
+
 // the LDS of one wave's walk: the current chunk's tubes, and with RAYS its rays' depth, travel time and stored-sign slowness
 struct TlTubes { double lo[64], hi[64], I[64]; };
 struct TlRays { double d[64], T[64], p[64]; };
 
-// The tubes of chunk c in column s into LDS: lane t loads ray m = c * TL_TUBES + t (its depth, g and launch slowness),
-// takes its neighbour's by a lane shuffle and forms tube t (an empty interval [0, 0) where the tube adds nothing).  TL and
-// the arrival passes all form their tubes here, so they see the same tubes and the same bits of I.
+// The tubes of chunk c in column s into LDS: lane t loads ray m = c * TL_TUBES + t, takes its neighbour's by a lane shuffle
+// and forms tube t (an empty interval [0, 0) where the tube adds nothing).
 template <bool RAYS>
 __device__ __forceinline__ void tl_chunk_tubes(const TlArgs& a, const Ctx<false, 0>& C, int s, double x, double r,
                                                int64_t c, int t, TlTubes& L, TlRays* Y)
 {
     const int64_t m = c * TL_TUBES + t;
-    double dz = NAN, g = NAN, q0 = NAN, p = NAN, T = NAN;
-    if (m < a.M) {
-        const int64_t n = a.keep ? (int64_t)a.keep[m] : m;
-        const int64_t i = tl_index(a, s, n);
-        dz = a.zsign * a.Z[i];
-        p = a.P[i];
-        if (RAYS) T = a.T[i];
-        q0 = a.p0[m];
-        if (dz == dz && p == p) {
-            double cv, cp;
-            C.lookup(x, dz, cv, cp);
-            const double pc = p * cv;
-            if (fabs(pc) < 1.0) g = fdiv(cv, fsqrt(1.0 - pc * pc));
-        }
-    }
+    const TlRay y = tl_ray<RAYS>(a, C, s, x, m, m < a.M);
+    const double dz = y.d, g = y.g, q0 = y.q0;
     const double dz1 = __shfl_down(dz, 1), g1 = __shfl_down(g, 1), q1 = __shfl_down(q0, 1);
     double lo = 0.0, hi = 0.0, I = 0.0;
     if (t < TL_TUBES && m + 1 < a.M && g == g && g1 == g1 && dz != dz1) {
@@ -123,67 +201,53 @@ __device__ __forceinline__ void tl_chunk_tubes(const TlArgs& a, const Ctx<false,
     L.I[t] = I;
     if (RAYS) {
         Y->d[t] = dz;
-        Y->T[t] = T;
-        Y->p[t] = -a.zsign * p;                    // RayFan.ps's sign whatever the fan kernel stored
+        Y->T[t] = y.T;
+        Y->p[t] = -a.zsign * y.p;                  // RayFan.ps's sign whatever the fan kernel stored
     }
     __syncthreads();
 }
 
-// The walk of one wave over column s for its band of receivers (lane t: receiver depth d): the chunks of the column in
-// order, those whose interval misses the band skipped, and for every tube u of a chunk, in order, that holds d,
-// visit(u).  The tubes of chunk c are then in L (and Y), tube u being rays c * TL_TUBES + u and + u + 1.
+// TL's walk (TL and both arrival passes): for every tube u of a chunk, in order, that holds the lane's receiver, visit(c, u);
+// the tubes of chunk c are then in L (and Y), tube u being rays c * TL_TUBES + u and + u + 1
 template <bool RAYS, typename Visit>
-__device__ __forceinline__ void tl_walk(const TlArgs& a, const Ctx<false, 0>& C, int slot, int s, double x, double r,
-                                        double d, int t, TlTubes& L, TlRays* Y, Visit visit)
+__device__ __forceinline__ void tl_walk(const TlArgs& a, const Ctx<false, 0>& C, const TlBand& b, TlTubes& L, TlRays* Y,
+                                        Visit visit)
 {
-    // the band's depth span (whatever the order of the depths)
-    const double dlo = tl_wave_min(d), dhi = tl_wave_max(d);
-    const double* bnd = a.bounds + 2 * (int64_t)slot * a.nchunk;
-    for (int64_t c0 = 0; c0 < a.nchunk; c0 += 64) {
-        bool hit = false;
-        if (c0 + t < a.nchunk) {
-            const double clo = bnd[2 * (c0 + t)], chi = bnd[2 * (c0 + t) + 1];
-            hit = (clo <= dhi) & (chi > dlo);      // a tube [lo, hi) of the chunk may hold a receiver of the band
-        }
-        unsigned long long mask = ballot64(hit);
-        while (mask) {
-            const int64_t c = c0 + __builtin_ctzll(mask);
-            mask &= mask - 1;
-            tl_chunk_tubes<RAYS>(a, C, s, x, r, c, t, L, Y);
-            for (int u = 0; u < TL_TUBES; u++)
-                if ((L.lo[u] <= d) & (d < L.hi[u])) visit(c, u);
-        }
-    }
+    tube_walk<1>(a, b.slot, b.d, b.t,
+                 // a tube [lo, hi) of the chunk may hold a receiver of the band
+                 [](double lo, double hi, double dlo, double dhi) { return (lo <= dhi) & (hi > dlo); },
+                 [&](int64_t c, int) {
+                     tl_chunk_tubes<RAYS>(a, C, b.s, b.x, b.r, c, b.t, L, Y);
+                     for (int u = 0; u < TL_TUBES; u++)
+                         if ((L.lo[u] <= b.d) & (b.d < L.hi[u])) visit(c, u);
+                 });
 }
 
-// pass 2: one wave per (column, band of 64 receivers)
+// TL's pass 2: one wave per (column, band of 64 receivers)
 __global__ void __launch_bounds__(64) pgr_tl_sum(EnvDev env, TlArgs a)
 {
     __shared__ TlTubes L;
-    const int s = blockIdx.x;
-    const int t = threadIdx.x;
-    const int64_t j = (int64_t)blockIdx.y * 64 + t;
-    const bool rcv = j < a.R;
-    const double d = rcv ? a.depths[j] : a.depths[a.R - 1];
-    const double x = a.x[s];
-    const double r = fabs(x - a.x[0]);
-    if (r == 0.0) {                                // the source's own column
-        if (rcv) a.out[j * a.S + s] = NAN;
+    const TlBand b = tl_band<false>(a);
+    if (b.r == 0.0) {                              // the source's own column
+        b.put(a, NAN);
         return;
     }
     const Ctx<false, 0> C(env, nullptr);
     double acc = 0.0;
-    tl_walk<false>(a, C, s, s, x, r, d, t, L, nullptr, [&](int64_t, int u) { acc = acc + L.I[u]; });
-    if (rcv) a.out[j * a.S + s] = acc;
+    tl_walk<false>(a, C, b, L, nullptr, [&](int64_t, int u) { acc = acc + L.I[u]; });
+    b.put(a, acc);
 }
 
-// pass 1 over a.ncol column slots (a.cols: HOST [ncol], uploaded here; NULL: all S columns), then `second` on `stream`; the
-// chunk bounds (and the column list) live in a stream-ordered allocation freed behind the second pass
-template <typename Second>
-static int tl_run(TlArgs a, const int32_t* cols, hipStream_t st, const char* who, Second second)
+// Pass 1 (`bounds`, chunks of `tubes` tubes) over the column slots -- the HOST list cols[ncol], uploaded here, or (cols
+// NULL) all S columns -- then pass 2, sum(env, g, extra...) with one wave per (slot, band of 64 receivers), on `st`.  The
+// chunk bounds (and the column list) live in a stream-ordered allocation freed behind pass 2.
+template <typename Args, typename... Extra>
+static int tube_run(const pgr_env* env, Args g, int tubes, void (*bounds)(Args), const int32_t* cols, int32_t ncol,
+                    hipStream_t st, const char* who, void (*sum)(EnvDev, Args, Extra...), Extra... extra)
 {
-    a.nchunk = (a.M - 1 + TL_TUBES - 1) / TL_TUBES;
-    if (!cols) a.ncol = a.S;
+    TlArgs& a = g;
+    a.nchunk = (a.M - 1 + tubes - 1) / tubes;
+    a.ncol = cols ? ncol : a.S;
     const size_t nb = (size_t)a.ncol * (size_t)a.nchunk * 16;
     void* b = nullptr;
     if (hipMallocAsync(&b, nb + (cols ? (size_t)a.ncol * sizeof(int32_t) : 0), st) != hipSuccess)
@@ -196,11 +260,11 @@ static int tl_run(TlArgs a, const int32_t* cols, hipStream_t st, const char* who
         e = hipMemcpyAsync((void*)a.cols, cols, (size_t)a.ncol * sizeof(int32_t), hipMemcpyHostToDevice, st);
     }
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(pgr_tl_bounds, dim3((unsigned)((a.nchunk + 3) / 4), (unsigned)a.ncol), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(bounds, dim3((unsigned)((a.nchunk + 3) / 4), (unsigned)a.ncol), dim3(256), 0, st, g);
         e = hipGetLastError();
     }
     if (e == hipSuccess) {
-        second(a);
+        hipLaunchKernelGGL(sum, dim3((unsigned)a.ncol, (unsigned)((a.R + 63) / 64)), dim3(64), 0, st, env->d, g, extra...);
         e = hipGetLastError();
     }
     (void)hipFreeAsync(b, st);
@@ -208,13 +272,7 @@ static int tl_run(TlArgs a, const int32_t* cols, hipStream_t st, const char* who
     return 0;
 }
 
-static int tl_run(const pgr_env* env, TlArgs a, hipStream_t st, const char* who)
-{
-    return tl_run(a, nullptr, st, who, [&](const TlArgs& b) {
-        hipLaunchKernelGGL(pgr_tl_sum, dim3((unsigned)b.S, (unsigned)((b.R + 63) / 64)), dim3(64), 0, st, env->d, b);
-    });
-}
-
+// the checks every tube entry makes; `out` is its first output
 static int tl_check(int64_t M, int32_t S, const double* p0, const double* depths, int64_t R, const void* out, const char* who)
 {
     if (!p0 || !depths || !out) return fail(std::string(who) + ": null argument");
@@ -225,15 +283,20 @@ static int tl_check(int64_t M, int32_t S, const double* p0, const double* depths
     return 0;
 }
 
-// a device-resident fan's TlArgs: waits for its kernel, runs the caller's argument `check` (the fan's M is known then),
-// uploads the keep list and the save ranges on first use (held by the handle); the caller holds f->m
-template <typename Check>
-static int tl_fan_args(pgr_fan* f, TlArgs& a, const char* who, Check check)
+// The prologue of the entries on a fan handle: a fan with trajectories; under its lock, once its kernel has finished (its M
+// is known then), tl_check and the entry's own check(S); the keep list and the save ranges uploaded on first use (held by
+// the handle); then run(env, a) with the fan's TlArgs and the receivers.
+template <typename Check, typename Run>
+static int tl_fan_entry(pgr_fan* f, const double* p0, const double* depths, int64_t R, const void* out, const char* who,
+                        Check check, Run run)
 {
+    if (!f) return fail(std::string(who) + ": null fan");
+    if (!f->save) return fail(std::string(who) + ": the fan was launched without trajectories (S = 0)");
+    std::lock_guard<std::mutex> lock(f->m);
     HIPCHK(hipSetDevice(f->env->device));
     int rc = fan_finish(f);
-    if (rc) return rc;
-    rc = check();
+    if (!rc) rc = tl_check(f->M, f->S, p0, depths, R, out, who);
+    if (!rc) rc = check(f->S);
     if (rc) return rc;
     if (f->M != f->N && !f->d_keep) {
         // the columns of the surviving rays, uploaded once per fan (freed with it): dropped rays are skipped in place
@@ -250,43 +313,58 @@ static int tl_fan_args(pgr_fan* f, TlArgs& a, const char* who, Check check)
         HIPCHK(hipMemcpy(f->d.r, r.data(), (size_t)f->S * sizeof(double), hipMemcpyHostToDevice));
         f->r_filled = true;
     }
-    a = TlArgs{};
+    TlArgs a{};
     a.Z = f->d.Z; a.P = f->d.P; a.T = f->d.T; a.keep = (f->M != f->N) ? f->d_keep : nullptr;
     a.N = f->N; a.M = f->M; a.S = f->S; a.blocked = f->blocked ? 1 : 0;
     a.zsign = (f->flags & PGR_STORED_SIGN) ? -1.0 : 1.0;
-    a.x = f->d.r;
-    return 0;
+    a.x = f->d.r; a.p0 = p0; a.depths = depths; a.R = R;
+    return run(f->env, a);
+}
+
+// The prologue of the entries on caller buffers z / p [S][N] (stored sign, every ray surviving), x [S] and with RAYS the
+// travel times T: an environment, the buffers, tl_check and the entry's own check(S); then run(env, a) on env's device.
+template <bool RAYS, typename Check, typename Run>
+static int tl_buffer_entry(const pgr_env* env, const double* T, const double* z, const double* p, int64_t n_rays,
+                           int32_t n_samples, const double* x, const double* p0, const double* depths, int64_t R,
+                           const void* out, const char* who, Check check, Run run)
+{
+    if (!env) return fail(std::string(who) + ": null environment");
+    if ((RAYS && !T) || !z || !p || !x) return fail(std::string(who) + ": null argument");
+    int rc = tl_check(n_rays, n_samples, p0, depths, R, out, who);
+    if (!rc) rc = check(n_samples);
+    if (rc) return rc;
+    HIPCHK(hipSetDevice(env->device));
+    TlArgs a{};
+    a.Z = z; a.P = p; a.T = T; a.keep = nullptr;
+    a.N = n_rays; a.M = n_rays; a.S = n_samples; a.blocked = 0;
+    a.zsign = -1.0;
+    a.x = x; a.p0 = p0; a.depths = depths; a.R = R;
+    return run(env, a);
+}
+
+static int tl_no_check(int32_t) { return 0; }
+
+static int tl_intensity(const pgr_env* env, TlArgs a, double* out, void* stream, const char* who)
+{
+    a.out = out;
+    return tube_run(env, a, TL_TUBES, pgr_tl_bounds, nullptr, 0, (hipStream_t)stream, who, pgr_tl_sum);
 }
 
 extern "C" int pgr_fan_intensity(pgr_fan* f, const double* p0, const double* depths, int64_t n_depths, double* out,
                                  void* stream)
 {
-    if (!f) return fail("pgr_fan_intensity: null fan");
-    if (!f->save) return fail("pgr_fan_intensity: the fan was launched without trajectories (S = 0)");
-    std::lock_guard<std::mutex> lock(f->m);
-    TlArgs a;
-    int rc = tl_fan_args(f, a, "pgr_fan_intensity",
-                         [&] { return tl_check(f->M, f->S, p0, depths, n_depths, out, "pgr_fan_intensity"); });
-    if (rc) return rc;
-    a.p0 = p0; a.depths = depths; a.R = n_depths; a.out = out;
-    return tl_run(f->env, a, (hipStream_t)stream, "pgr_fan_intensity");
+    const char* who = "pgr_fan_intensity";
+    return tl_fan_entry(f, p0, depths, n_depths, out, who, tl_no_check,
+                        [&](const pgr_env* e, TlArgs a) { return tl_intensity(e, a, out, stream, who); });
 }
 
 extern "C" int pgr_intensity_device(pgr_env* env, const double* z, const double* p, int64_t n_rays, int32_t n_samples,
                                     const double* x, const double* p0, const double* depths, int64_t n_depths, double* out,
                                     void* stream)
 {
-    if (!env) return fail("pgr_intensity_device: null environment");
-    if (!z || !p || !x) return fail("pgr_intensity_device: null argument");
-    int rc = tl_check(n_rays, n_samples, p0, depths, n_depths, out, "pgr_intensity_device");
-    if (rc) return rc;
-    HIPCHK(hipSetDevice(env->device));
-    TlArgs a{};
-    a.Z = z; a.P = p; a.keep = nullptr;
-    a.N = n_rays; a.M = n_rays; a.S = n_samples; a.blocked = 0;
-    a.zsign = -1.0;
-    a.x = x; a.p0 = p0; a.depths = depths; a.R = n_depths; a.out = out;
-    return tl_run(env, a, (hipStream_t)stream, "pgr_intensity_device");
+    const char* who = "pgr_intensity_device";
+    return tl_buffer_entry<false>(env, nullptr, z, p, n_rays, n_samples, x, p0, depths, n_depths, out, who, tl_no_check,
+                                  [&](const pgr_env* e, TlArgs a) { return tl_intensity(e, a, out, stream, who); });
 }
 
 #endif  // PGR_TL_H

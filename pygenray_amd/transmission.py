@@ -17,41 +17,37 @@ _NO_FE_MSG = ("Flat earth transformation has not been applied. Set `flat_earth_t
               "when creating the OceanEnvironment2D object.")
 
 
-def _check_arguments(rays, receiver_depths, environment, flatearth, who="transmission_loss"):
-    """Everything that can be refused without a GPU; -> (depths, save ranges x, source depth)."""
-    d = np.asarray(receiver_depths, dtype=float)
-    if d.ndim != 1 or len(d) == 0:
-        raise ValueError("receiver_depths must be a non-empty 1-D sequence")
-    if not np.all(np.isfinite(d)):
-        raise ValueError("receiver_depths must be finite")
-    if not np.all(np.diff(d) > 0):
-        raise ValueError("receiver_depths must be strictly ascending")
-    if flatearth and not hasattr(environment, "sound_speed_fe"):
-        raise ValueError(_NO_FE_MSG)
-    if len(rays) < 2:
-        raise ValueError(f"{who} needs a fan of at least 2 rays (one ray tube)")
-    sd = np.asarray(rays.source_depths, dtype=float)
-    if not np.all(sd == sd[0]):
-        raise ValueError("the fan mixes source depths: ray tubes need one source")
-    r = rays.__dict__.get("_r")
-    if r is not None and rays.__dict__.get("_rs") is None:
-        x = np.asarray(r, dtype=float)          # (a device fan: one save grid by construction)
-    else:
-        rs = np.asarray(rays.rs, dtype=float)
-        x = rs[0]
-        if not np.array_equal(rs, np.broadcast_to(x, rs.shape)):
-            raise ValueError("the rows of rays.rs differ: the fan must share one save grid")
-    return np.ascontiguousarray(d), x, float(sd[0])
-
-
 class _FanFrame:
-    """A fan checked for the tube kernels (`who` names the caller in errors): the receiver depths and the save ranges x.
-    ``to_device`` then sets up the frame the fan was traced in -- xf (mirrored for a backwards fan), the EnvHandle and its
-    tables (cin, rin, zin), the launch slowness p0, the device copies of p0 and the depths, the torch stream and the fan's
-    device handle (None for a host fan)."""
+    """A fan checked for the tube kernels (`who` names the caller in errors): the receiver depths, the save ranges x and the
+    source depth -- everything that can be refused without a GPU.  ``to_device`` then sets up the frame the fan was traced
+    in -- xf (mirrored for a backwards fan), the EnvHandle and its tables (cin, rin, zin), the launch slowness p0, the
+    device copies of p0 and the depths, the torch stream and the fan's device handle (None for a host fan) -- and ``run``
+    calls a tube entry there."""
 
     def __init__(self, rays, receiver_depths, environment, flatearth, who):
-        self.depths, self.x, self.source_depth = _check_arguments(rays, receiver_depths, environment, flatearth, who)
+        d = np.asarray(receiver_depths, dtype=float)
+        if d.ndim != 1 or len(d) == 0:
+            raise ValueError("receiver_depths must be a non-empty 1-D sequence")
+        if not np.all(np.isfinite(d)):
+            raise ValueError("receiver_depths must be finite")
+        if not np.all(np.diff(d) > 0):
+            raise ValueError("receiver_depths must be strictly ascending")
+        if flatearth and not hasattr(environment, "sound_speed_fe"):
+            raise ValueError(_NO_FE_MSG)
+        if len(rays) < 2:
+            raise ValueError(f"{who} needs a fan of at least 2 rays (one ray tube)")
+        sd = np.asarray(rays.source_depths, dtype=float)
+        if not np.all(sd == sd[0]):
+            raise ValueError("the fan mixes source depths: ray tubes need one source")
+        r = rays.__dict__.get("_r")
+        if r is not None and rays.__dict__.get("_rs") is None:
+            x = np.asarray(r, dtype=float)          # (a device fan: one save grid by construction)
+        else:
+            rs = np.asarray(rays.rs, dtype=float)
+            x = rs[0]
+            if not np.array_equal(rs, np.broadcast_to(x, rs.shape)):
+                raise ValueError("the rows of rays.rs differ: the fan must share one save grid")
+        self.depths, self.x, self.source_depth = np.ascontiguousarray(d), x, float(sd[0])
         self.rays, self.environment, self.flatearth = rays, environment, flatearth
 
     def to_device(self, device):
@@ -65,23 +61,40 @@ class _FanFrame:
         c_source = bilinear_interp(self.xf[0], self.source_depth, rin, zin, cin)
         self.p0 = _initial_slowness(self.rays.thetas, c_source)
         self.dev = torch.device("cuda", self.env.device)
-        self.d_p0 = torch.from_numpy(np.ascontiguousarray(self.p0)).to(self.dev)
-        self.d_depths = torch.from_numpy(self.depths).to(self.dev)
+        self.d_p0 = self.upload(self.p0)
+        self.d_depths = self.upload(self.depths)
         self.stream = torch.cuda.current_stream(self.dev).cuda_stream
         self.handle = self.rays.__dict__.get("_dev")
         if self.handle is not None and self.handle._env is not self.env:
             raise ValueError("the fan was traced in another environment (or flatearth setting) than the one given")
+        self._host = {}
         return self
 
-    def upload_rows(self, a):
-        """A host fan's (M, S) array as the (S, M) device rows the kernels read (the transposed view shoot_rays hands out is
-        that layout already)."""
+    def upload(self, a):
         import torch
-        return torch.from_numpy(np.ascontiguousarray(np.asarray(a, dtype=float).T)).to(self.dev)
+        return torch.from_numpy(np.ascontiguousarray(a, dtype=float)).to(self.dev)
 
-    def upload_x(self):
+    def _host_fan(self, name):
+        """A host fan's array `name` on the device, uploaded once per frame: the (M, S) arrays as the (S, M) rows the kernels
+        read (the transposed view shoot_rays hands out is that layout already), xf as it is."""
+        if name not in self._host:
+            a = self.xf if name == "xf" else np.asarray(getattr(self.rays, name), dtype=float).T
+            self._host[name] = self.upload(a)
+        return self._host[name].data_ptr()
+
+    def run(self, entry, *args):
+        """Tube entry `entry` on the fan, with p0, the arguments after it and the stream: ``FanHandle.<entry>`` on a
+        device-resident fan, else ``_lib.<entry>_device`` on the host fan's trajectories (ts only for ``arrivals``)."""
+        args = (self.d_p0.data_ptr(),) + args + (self.stream,)
+        if self.handle is not None:
+            return getattr(self.handle, entry)(*args)
+        fan = [self._host_fan(k) for k in (("ts", "zs", "ps") if entry == "arrivals" else ("zs", "ps"))]
+        getattr(_lib, entry + "_device")(self.env, *fan, len(self.rays), len(self.x), self._host_fan("xf"), *args)
+
+    def image(self):
+        """an empty (R, S) float64 device array: an intensity image's output"""
         import torch
-        return torch.from_numpy(np.ascontiguousarray(self.xf)).to(self.dev)
+        return torch.empty((len(self.depths), len(self.x)), dtype=torch.float64, device=self.dev)
 
     def bottom(self):
         """The bottom depth at each save range in the frame the fan was traced in (flat-earth, mirrored for a backwards fan):
@@ -90,6 +103,15 @@ class _FanFrame:
         if self.backwards:
             depths, depth_ranges = _mirror_envi_arrays(cin, cpin, rin, depths, depth_ranges, angles)[3:5]
         return np.array([linear_interp(float(v), depth_ranges, depths) for v in self.xf])
+
+
+def _db(out, intensity):
+    """an intensity image on the device -> the host array: I itself, or -10 log10(I) dB"""
+    I = out.cpu().numpy()
+    if intensity:
+        return I
+    with np.errstate(divide="ignore"):
+        return -10.0 * np.log10(I)
 
 
 def transmission_loss(rays, receiver_depths, environment, flatearth=True, device=0, intensity=False):
@@ -106,21 +128,9 @@ def transmission_loss(rays, receiver_depths, environment, flatearth=True, device
     backwards fan).  Known artefacts of the method: spikes at caustics and a strip about one tube wide along the surface
     and the bottom.  A device-resident fan is processed where it is and stays device resident."""
     f = _FanFrame(rays, receiver_depths, environment, flatearth, "transmission_loss").to_device(device)
-    import torch
-
-    R, S = len(f.depths), len(f.x)
-    out = torch.empty((R, S), dtype=torch.float64, device=f.dev)
-    if f.handle is not None:
-        f.handle.intensity(f.d_p0.data_ptr(), f.d_depths.data_ptr(), R, out.data_ptr(), f.stream)
-    else:
-        z, p, d_x = f.upload_rows(rays.zs), f.upload_rows(rays.ps), f.upload_x()
-        _lib.intensity_device(f.env, z.data_ptr(), p.data_ptr(), len(rays), S, d_x.data_ptr(), f.d_p0.data_ptr(),
-                              f.d_depths.data_ptr(), R, out.data_ptr(), f.stream)
-    I = out.cpu().numpy()
-    if intensity:
-        return I
-    with np.errstate(divide="ignore"):
-        return -10.0 * np.log10(I)
+    out = f.image()
+    f.run("intensity", f.d_depths.data_ptr(), len(f.depths), out.data_ptr())
+    return _db(out, intensity)
 
 
 def beam_transmission_loss(rays, receiver_depths, environment, flatearth=True, device=0, intensity=False, min_width=10.0):
@@ -150,22 +160,9 @@ def beam_transmission_loss(rays, receiver_depths, environment, flatearth=True, d
     if not (np.isfinite(w) and w > 0):
         raise ValueError("min_width must be finite and > 0")
     f = _FanFrame(rays, receiver_depths, environment, flatearth, "beam_transmission_loss").to_device(device)
-    import torch
-
-    R, S = len(f.depths), len(f.x)
-    out = torch.empty((R, S), dtype=torch.float64, device=f.dev)
-    d_b = torch.from_numpy(f.bottom()).to(f.dev)
-    if f.handle is not None:
-        f.handle.beam_intensity(f.d_p0.data_ptr(), d_b.data_ptr(), f.d_depths.data_ptr(), R, w, out.data_ptr(), f.stream)
-    else:
-        z, p, d_x = f.upload_rows(rays.zs), f.upload_rows(rays.ps), f.upload_x()
-        _lib.beam_intensity_device(f.env, z.data_ptr(), p.data_ptr(), len(rays), S, d_x.data_ptr(), f.d_p0.data_ptr(),
-                                   d_b.data_ptr(), f.d_depths.data_ptr(), R, w, out.data_ptr(), f.stream)
-    I = out.cpu().numpy()
-    if intensity:
-        return I
-    with np.errstate(divide="ignore"):
-        return -10.0 * np.log10(I)
+    out, d_b = f.image(), f.upload(f.bottom())
+    f.run("beam_intensity", d_b.data_ptr(), f.d_depths.data_ptr(), len(f.depths), w, out.data_ptr())
+    return _db(out, intensity)
 
 
 __all__ = ["transmission_loss", "beam_transmission_loss"]

@@ -7,21 +7,10 @@ import pytest
 import arrivals_reference as ar
 import tl_reference as tlr
 from test_arrivals_host import check_gradient_arrivals
-from test_transmission_loss import (DEPTHS, SYN_R, SYN_Z, _env, munk_env, sloping_env, sloping_env_shallow_table,
-                                    synthetic_fan, syn_env)  # noqa: F401  (syn_env: a fixture)
+from tube_gpu import (DEPTHS, SYN_R, SYN_Z, _device_arrivals, _env, munk_env, pr, sloping_env,  # noqa: F401
+                      sloping_env_shallow_table, syn_env, synthetic_fan)  # (pr, syn_env: fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def pr():
-    from pygenray_amd import _lib
-    if _lib.ARITH != "reference":
-        pytest.skip("bit parity is claimed for the reference arithmetic only (PGR_ARITH=contracted: tests/test_contracted_arith.py)")
-    _lib.load()
-    assert _lib.device_count() >= 1
-    import pygenray_amd
-    return pygenray_amd
 
 
 def _same_arrivals(a, b):
@@ -55,32 +44,6 @@ def _synthetic_t(M, S, seed):
         T[S - 1, M // 2] = np.nan
         T[0, 1] = np.nan
     return T
-
-
-def _device_arrivals(env, t, z, p, x, p0, depths, cols):
-    import torch
-    from pygenray_amd import _lib
-    dev = torch.device("cuda", env.device)
-    d = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev) for a in (t, z, p, x, p0, depths)]
-    S, M = z.shape
-    R, n = len(depths), len(cols)
-    stream = torch.cuda.current_stream(dev).cuda_stream
-    counts = torch.full((R * n,), -1, dtype=torch.int64, device=dev)
-    _lib.arrival_counts_device(env, d[1].data_ptr(), d[2].data_ptr(), M, S, d[3].data_ptr(), d[4].data_ptr(),
-                               d[5].data_ptr(), R, cols, counts.data_ptr(), stream)
-    offsets = torch.zeros(R * n + 1, dtype=torch.int64, device=dev)
-    torch.cumsum(counts, 0, out=offsets[1:])
-    total = int(offsets[-1].item())
-    out = dict(offsets=offsets.cpu().numpy(), tube=np.zeros(0, np.int32), w=np.zeros(0), T=np.zeros(0), p=np.zeros(0),
-               I=np.zeros(0))
-    if total:
-        tube = torch.full((total,), -1, dtype=torch.int32, device=dev)
-        f = [torch.full((total,), -1.0, dtype=torch.float64, device=dev) for _ in range(4)]
-        _lib.arrivals_device(env, d[0].data_ptr(), d[1].data_ptr(), d[2].data_ptr(), M, S, d[3].data_ptr(),
-                             d[4].data_ptr(), d[5].data_ptr(), R, cols, offsets.data_ptr(), total, tube.data_ptr(),
-                             *(a.data_ptr() for a in f), stream)
-        out.update(tube=tube.cpu().numpy(), **{k: a.cpu().numpy() for k, a in zip(("w", "T", "p", "I"), f)})
-    return out
 
 
 SYN_CASES = ([(M, 5, 129, False) for M in (2, 3, 63, 64, 65, 127, 128, 4033, 4034, 8300)]

@@ -10,40 +10,12 @@ import beam_reference as bref
 import tl_reference as tlr
 from pygenray_amd.host_physics import bilinear_interp
 from pygenray_amd.launch_rays import _initial_slowness
-from test_transmission_loss import (SYN_R, SYN_Z, _env, munk_env, sloping_env, sloping_env_shallow_table,
-                                    synthetic_fan, syn_env)  # noqa: F401  (syn_env: a fixture)
+from tube_gpu import (SYN_R, SYN_Z, _device_beams, _env, _same, munk_env, pr, sloping_env,  # noqa: F401
+                      sloping_env_shallow_table, syn_env, synthetic_fan)  # (pr, syn_env: fixtures)
 
 pytestmark = pytest.mark.gpu
 
 DEPTHS = np.linspace(-150.0, 5850.0, 600)           # some above the surface and below the bottom
-
-
-@pytest.fixture(scope="module")
-def pr():
-    from pygenray_amd import _lib
-    if _lib.ARITH != "reference":
-        pytest.skip("bit parity is claimed for the reference arithmetic only (PGR_ARITH=contracted: tests/test_contracted_arith.py)")
-    _lib.load()
-    assert _lib.device_count() >= 1
-    import pygenray_amd
-    return pygenray_amd
-
-
-def _same(a, b):
-    return np.array_equal(a, b, equal_nan=True)
-
-
-def _device_beams(env, z, p, x, p0, bottom, depths, w_min):
-    import torch
-    from pygenray_amd import _lib
-    dev = torch.device("cuda", env.device)
-    t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev) for a in (z, p, x, p0, bottom, depths)]
-    S, M = z.shape
-    out = torch.full((len(depths), S), -1.0, dtype=torch.float64, device=dev)
-    _lib.beam_intensity_device(env, t[0].data_ptr(), t[1].data_ptr(), M, S, t[2].data_ptr(), t[3].data_ptr(),
-                               t[4].data_ptr(), t[5].data_ptr(), len(depths), w_min, out.data_ptr(),
-                               torch.cuda.current_stream(dev).cuda_stream)
-    return out.cpu().numpy()
 
 
 def _check_synthetic(env, cin, z, p, x, p0, bottom, depths, w_min):

@@ -5,47 +5,10 @@ import numpy as np
 import pytest
 
 import tl_reference as tlr
+from tube_gpu import (DEPTHS, SYN_R, SYN_Z, _device_intensity, _env, _same, munk_env, pr, sloping_env,  # noqa: F401
+                      sloping_env_shallow_table, syn_env, synthetic_fan)  # (pr, syn_env: fixtures)
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def pr():
-    from pygenray_amd import _lib
-    if _lib.ARITH != "reference":
-        pytest.skip("bit parity is claimed for the reference arithmetic only (PGR_ARITH=contracted: tests/test_contracted_arith.py)")
-    _lib.load()
-    assert _lib.device_count() >= 1
-    import pygenray_amd
-    return pygenray_amd
-
-
-def _env(pr, z, r, cin, br, bd):
-    ssp = pr.DataArray(cin, dims=["range", "depth"], coords={"range": r, "depth": z})
-    bathy = pr.DataArray(bd, dims=["range"], coords={"range": br})
-    return pr.OceanEnvironment2D(ssp, bathy, flat_earth_transform=False)
-
-
-def munk_env(pr, ztop=6000.0):
-    """range-independent Munk, 5000 m flat bottom: LDS tables, rows layout"""
-    z = np.arange(0, ztop, 1.0)
-    r = np.linspace(0, 200e3, 100)
-    return _env(pr, z, r, np.tile(pr.munk_ssp(z), (100, 1)), r, np.full(100, 5000.0))
-
-
-def sloping_env(pr):
-    """range-dependent Munk over a sloping bottom: tables in HBM, sample-blocked layout"""
-    z = np.linspace(0, 5500, 1377)
-    r = np.linspace(0, 200e3, 33)
-    br = np.linspace(0, 200e3, 9)
-    return _env(pr, z, r, np.array([pr.munk_ssp(z, 1300 + 5e-4 * ri) for ri in r]), br, 4800 + 300 * np.sin(br / 40e3))
-
-
-DEPTHS = np.linspace(-150.0, 5850.0, 1000)          # some above the surface and below the bottom
-
-
-def _same(a, b):
-    return np.array_equal(a, b, equal_nan=True)
 
 
 def test_isovelocity_fan_end_to_end_matches_the_image_sum(pr):
@@ -179,92 +142,6 @@ def test_value_errors(pr):
 # last chunk full or hold one tube, and give 64 / 65 chunks (M = 4033 / 4034: one / two ballot rounds); 8300 rays take
 # three rounds.  The receiver counts make the last band hold 1 / 63 / 64 receivers, and 4200 take more than 64 bands.
 
-SYN_R = np.linspace(0.0, 60e3, 13)                           # uniform range grid
-SYN_Z = np.concatenate([np.arange(0.0, 1000.0, 20.0), np.arange(1000.0, 5001.0, 50.0)])    # non-uniform depth grid
-
-
-@pytest.fixture(scope="module")
-def syn_env(pr):
-    """a small range-dependent table (tables in HBM): smooth, positive, so that the bilinear look-up of c matters"""
-    from pygenray_amd import _lib
-    rr, zz = np.meshgrid(SYN_R, SYN_Z, indexing="ij")
-    cin = 1490.0 + 0.017 * zz + 8.0 * np.sin(2 * np.pi * rr / 40e3) + 6.0 * np.exp(-((zz - 1200.0) / 500.0) ** 2)
-    cpin = np.gradient(cin, SYN_Z, axis=1, edge_order=1)
-    nr = len(SYN_R)
-    return _lib.EnvHandle(cin, cpin, SYN_R, SYN_Z, np.full(nr, 5000.0), SYN_R.copy(), np.zeros(nr)), cin
-
-
-def _p_with_pc(c, target_above):
-    """a slowness p > 0 with fl(p c) == 1.0 exactly (target_above False) or fl(p c) just above 1 (True)"""
-    p = 1.0 / c
-    for _ in range(8):
-        pc = p * c
-        if (pc > 1.0) if target_above else (pc == 1.0):
-            return p
-        p = np.nextafter(p, np.inf if pc <= 1.0 else -np.inf)
-    raise AssertionError(f"no p with p c {'>' if target_above else '=='} 1 for c = {c!r}")
-
-
-def synthetic_fan(M, S, R, seed, cin, shuffle=False):
-    """(z, p) [S][M] stored convention, x [S], p0 [M], receiver depths [R] exercising the kernel's edges.  Column s follows
-    one of four patterns: a monotone fan (chunks mostly miss a band), a fold (ray order reverses between neighbours),
-    a scramble (tubes of every chunk overlap, every receiver sums across all chunks and rounds) and a fan clustered near
-    the surface.  All finite depths lie in [-200, 5200] m, the ranges in the table's span."""
-    rng = np.random.default_rng(seed)
-    u = np.linspace(0.0, 1.0, M)
-    x = np.linspace(0.0, 55e3, S)
-    if S >= 4:
-        x[S - 2] = x[0]                                       # a column s > 0 with r_s == 0: NaN
-    d = np.empty((S, M))
-    for s in range(S):
-        kind = s % 4
-        if kind == 0:
-            d[s] = 2500.0 + 2400.0 * (2 * u - 1) + rng.uniform(-0.1, 0.1, M)
-        elif kind == 1:
-            d[s] = 2500.0 + 2000.0 * np.sin(3 * np.pi * u + s)
-        elif kind == 2:
-            d[s] = rng.uniform(-200.0, 5200.0, M)
-        else:
-            d[s] = 100.0 + 4000.0 * u ** 3
-    p = np.sin(np.radians(rng.uniform(-30.0, 30.0, (S, M)))) / 1500.0
-    p0 = np.sin(np.radians(np.linspace(-25.0, 25.0, M) + rng.uniform(-1e-3, 1e-3, M))) / 1500.0
-    # the branches where a tube adds nothing, mid-ray and on the seam of chunks 0 / 1 where the fan is long enough
-    cols = [s for s in range(S) if x[s] != x[0]]
-    if M >= 8 and cols:
-        d[cols[0], M // 2] = np.nan                                  # NaN depth, finite p
-        p[cols[1 % len(cols)], M // 3] = np.nan                      # NaN p, finite depth
-        s = cols[2 % len(cols)]
-        d[s, M // 4 + 1] = d[s, M // 4]                              # equal depths of neighbours
-        for j, (k, above) in enumerate([(M // 5, False), (M - 3, True), (min(62, M - 1), False), (min(63, M - 1), True)]):
-            s = cols[j % len(cols)]
-            if np.isfinite(d[s, k]) and np.isfinite(p[s, k]):
-                c = tlr.bilinear(x[s], d[s, k], SYN_R, SYN_Z, cin)
-                p[s, k] = (1 - 2 * (j & 1)) * _p_with_pc(c, above)  # |p c| == 1 and just above 1, both signs
-    if M >= 4 * 63 + 1:
-        d[S - 1, 2 * 63: 3 * 63 + 1] = np.nan                       # chunk 2 all NaN in the last column: bounds [+inf, -inf]
-    depths = np.linspace(-300.0, 5300.0, R) if R > 1 else np.array([2500.0])   # the first / last above / below every sample
-    if R >= 8:
-        s = cols[0] if cols else 0
-        fin = d[s][np.isfinite(d[s])]
-        on = rng.choice(fin, R // 4, replace=len(fin) < R // 4)
-        depths[1: 1 + len(on)] = on                                 # receivers on sample depths: one tube's lo, another's hi
-    depths = rng.permutation(depths) if shuffle else np.sort(depths)
-    assert len(depths) == R and np.isfinite(depths).all()
-    return -d, p, x, p0, depths
-
-
-def _device_intensity(env, z, p, x, p0, depths):
-    import torch
-    from pygenray_amd import _lib
-    dev = torch.device("cuda", env.device)
-    t = [torch.from_numpy(np.ascontiguousarray(a, dtype=np.float64)).to(dev) for a in (z, p, x, p0, depths)]
-    S, M = z.shape
-    out = torch.full((len(depths), S), -1.0, dtype=torch.float64, device=dev)
-    _lib.intensity_device(env, t[0].data_ptr(), t[1].data_ptr(), M, S, t[2].data_ptr(), t[3].data_ptr(), t[4].data_ptr(),
-                          len(depths), out.data_ptr(), torch.cuda.current_stream(dev).cuda_stream)
-    return out.cpu().numpy()
-
-
 SYN_CASES = ([(M, 5, 129, False) for M in (2, 3, 63, 64, 65, 126, 127, 128, 4033, 4034, 4035, 8300)]
              + [(500, 5, R, False) for R in (1, 63, 64, 65, 128, 129, 4200)]
              + [(300, S, 100, False) for S in (1, 2, 5, 100)]
@@ -300,14 +177,6 @@ def test_several_ballot_rounds_bit_identical_to_the_restatement(pr, case):
     I = pr.transmission_loss(fan, depths, env, flatearth=False, intensity=True)
     assert _same(I, tlr.fan_intensity(fan, depths, env, flatearth=False))
     assert (I[:, 1:] > 0).mean() > 0.3
-
-
-def sloping_env_shallow_table(pr):
-    """sloping_env with its depth table cut at 4200 m, above the sea floor: the deep rays leave it and are dropped"""
-    z = np.linspace(0, 4200, 1051)
-    r = np.linspace(0, 200e3, 33)
-    br = np.linspace(0, 200e3, 9)
-    return _env(pr, z, r, np.array([pr.munk_ssp(z, 1300 + 5e-4 * ri) for ri in r]), br, 4800 + 300 * np.sin(br / 40e3))
 
 
 def test_dropped_rays_on_the_sample_blocked_layout(pr):
