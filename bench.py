@@ -1,8 +1,8 @@
 #!/usr/bin/env python3
 """Headline benchmark: ray-steps/sec of a 1e5-ray Munk fan to 1000 km (BASELINE.json configs[1]),
-plus the eigenray wall-clock of configs[3].
+plus (with --full) the eigenray wall-clock of configs[3].
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
 
 With N > 1 and no WORLD_SIZE in the environment this process only LAUNCHES the N ranks (one per
 GPU, `python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 ...`,
@@ -19,12 +19,18 @@ the RCCL all-gather of the 40-byte end records (pygenray_amd/distributed.py); `-
 One JSON line on rank 0: value = accepted RK45 steps of all rays on all ranks / wall time (max over
 ranks, barrier + synchronize on both sides).  `roofline` prices the fan kernel against HBM with
 SURVEY.md 8(d)'s algorithmic bytes, `roofline_valu` against the fp64 VALU issue rate that really
-bounds it; `cpu_baseline` is the reference's own call pattern (scipy.integrate.solve_ivp, RK45,
-4 terminal events, NumPy right-hand side: oracle/scipy_port.py -- the reference itself cannot
-travel to the GPU box) on all usable host cores, `cpu_baseline_c` the C/OpenMP oracle; `eigenray`
-the wall-clock of configs[3] (1e6-angle fan + regula-falsi refinement); `legs` = the kernel instances users hit
-beside the headline one (default flat-earth grid, configs[2], 1e6 rays), a few passes each, and `lone_wave_ms` the
-64 steepest rays alone (the floor of the fan's kernel time); rank 0 at N = 1 only.
+bounds it (both from the timed steps and the committed PMC passes: no runs of their own).
+
+A plain run does only that: set up, warm up, time the steps, dump (--dump-outputs), print the line.
+`--full` adds everything that takes runs of its own.  At N = 1 (rank 0): `cpu_baseline`, the
+reference's own call pattern (scipy.integrate.solve_ivp, RK45, 4 terminal events, NumPy right-hand
+side: oracle/scipy_port.py -- the reference itself is not part of this repository) on all usable
+host cores, and `cpu_baseline_c`, the C/OpenMP oracle; `eigenray`, the wall-clock of configs[3]
+(1e6-angle fan + regula-falsi refinement); `legs` = the kernel instances users hit beside the
+headline one (default flat-earth grid, configs[2], 1e6 rays), a few passes each, the drop-in API
+and the FMA-contracted build, and `lone_wave_ms` the 64 steepest rays alone (the floor of the
+fan's kernel time).  At N > 1 (all ranks): `eigenray_sharded` and `legs.config4`.
+`--no-cpu-baseline`, `--no-eigenray` and `--no-legs` leave parts of --full out.
 """
 import argparse
 import json
@@ -67,13 +73,17 @@ def parse_args(argv=None):
     ap.add_argument("--flat-earth", action="store_true",
                     help="the configs[1] tables after OceanEnvironment2D's default flat-earth transform (non-uniform zin, "
                          "kernel ZM = 5): what pr.shoot_rays(...) integrates with the reference's default arguments; not the headline workload")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-eigenray", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline figure does not need: CPU baselines, the eigenray wall-clock, the extra "
+                         "kernel, API and FMA legs and the lone wave (N = 1); the sharded eigenray search and configs[4] (N > 1)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(with --full) skip the CPU baselines")
+    ap.add_argument("--no-eigenray", action="store_true", help="(with --full) skip the eigenray leg")
     ap.add_argument("--blocked", action="store_true",
                     help="(with --range-dependent) trajectories in the sample-blocked layout [S/4][N][4] (PGR_SAMPLE_BLOCKED): what the "
                          "range_dependent leg's `trajectories` entry times")
-    ap.add_argument("--no-legs", action="store_true", help="skip the extra kernel legs (flat-earth default grid, configs[2], 1e6 rays, lone wave)")
-    ap.add_argument("--eigen-rays", type=int, default=1_000_000, help="fan size of the eigenray leg (configs[3])")
+    ap.add_argument("--no-legs", action="store_true",
+                    help="(with --full) skip the extra kernel legs (flat-earth default grid, configs[2], 1e6 rays, lone wave)")
+    ap.add_argument("--eigen-rays", type=int, default=1_000_000, help="fan size of the eigenray leg (configs[3], with --full)")
     ap.add_argument("--waves-per-block", type=int, default=0)
     ap.add_argument("--backend", default="nccl", help="torch.distributed backend (nccl = RCCL; tests rehearse with gloo)")
     ap.add_argument("--launcher-only", action="store_true", help="(tests) start the ranks, let them report, do no GPU work")
@@ -84,6 +94,10 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be >= 1 and --warmup >= 0")
+    # what --full adds, part by part (a plain run measures the headline alone)
+    args.cpu_baseline = args.full and not args.no_cpu_baseline
+    args.eigenray = args.full and not args.no_eigenray
+    args.legs = args.full and not args.no_legs
     return args
 
 
@@ -627,7 +641,7 @@ def main(argv=None):
     # of the end records puts the fan on every rank, every rank brackets on the whole fan, the brackets are dealt to the
     # ranks for the device-resident false-position loop, one small gather collects the eigenrays
     eig_sharded = None
-    if use_dist and not args.no_eigenray:
+    if use_dist and args.eigenray:
         from pygenray_amd.distributed import shoot_rays_sharded, find_eigenrays_sharded
         angles = np.linspace(-20, 20, args.eigen_rays)
         for _ in range(2):   # second run: tables resident, buffers allocated
@@ -651,9 +665,9 @@ def main(argv=None):
                        "config": "configs[3] sharded: pygenray_amd.distributed.shoot_rays_sharded (strided shards, all-gather "
                                  "of 40-byte end records) + find_eigenrays_sharded (brackets dealt to the ranks)"}
 
-    # configs[4] (1e6 rays per GPU, end records, histogram all-reduce, all-gather): a leg of every N > 1 run
+    # configs[4] (1e6 rays per GPU, end records, histogram all-reduce, all-gather): a leg of every N > 1 --full run
     cfg4 = None
-    if use_dist and world > 1 and not args.no_legs:
+    if use_dist and world > 1 and args.legs:
         cfg4 = config4_leg(env, arrs, rank, world, fence)
 
     if rank == 0:
@@ -740,10 +754,10 @@ def main(argv=None):
             out["dump_outputs"] = dumped
         if args.histogram and hist is not None:
             out["histogram"] = {"bins": HIST_BINS, "range_s": [T_LO, T_HI], "counted_rays": int(hist.sum().item())}
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_scipy(arrs)
             out["cpu_baseline_c"] = cpu_baseline_c(arrs)
-        if world == 1 and not args.no_eigenray:
+        if world == 1 and args.eigenray:
             out["eigenray"] = eigenray_leg(env_obj, args.eigen_rays)
         if eig_sharded is not None:
             out["eigenray_sharded"] = eig_sharded
@@ -751,7 +765,7 @@ def main(argv=None):
             out["ranks_joined"] = ranks_joined      # (from the all-reduce every rank took part in at start-up)
         if cfg4 is not None:
             out.setdefault("legs", {})["config4"] = cfg4
-        if world == 1 and not args.no_legs:
+        if world == 1 and args.legs:
             del fan   # (2.4 GB of trajectories back before the legs allocate theirs)
             legs, lone = extra_legs()
             legs["api"] = api_leg(env_obj)

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-/root/repo}
 TAG=${1:-ev}
 cd $R
 O=gpurun_out/${TAG}_c; mkdir -p $O
-timeout -k 10 600 python bench.py > $O/bench_line.json 2> $O/bench.err; echo "bench rc $?"
+timeout -k 10 600 python bench.py --full > $O/bench_line.json 2> $O/bench.err; echo "bench rc $?"
 timeout -k 10 300 python bench.py --range-dependent --no-cpu-baseline --no-eigenray --no-legs > $O/bench_line_config2.json 2>> $O/bench.err; echo "rc $?"
 timeout -k 10 300 python bench.py --range-dependent --blocked --no-cpu-baseline --no-eigenray --no-legs > $O/bench_line_config2_blocked.json 2>> $O/bench.err; echo "rc $?"
 timeout -k 10 300 python bench.py --flat-earth --no-cpu-baseline --no-eigenray --no-legs > $O/bench_line_flatearth.json 2>> $O/bench.err; echo "rc $?"

@@ -1358,7 +1358,7 @@ def test_sharded_api_two_ranks_on_one_gpu_equal_the_single_process_api(lib, tmp_
 
 
 def test_bench_two_ranks_on_one_gpu_carries_the_multi_gpu_legs(lib):
-    """`python bench.py --gpus 2` end to end, the way the driver's N > 1 runs go (the launcher starts the ranks, rank 0 prints ONE
+    """`python bench.py --gpus 2 --full` end to end, as an N > 1 run goes (the launcher starts the ranks, rank 0 prints ONE
     JSON line) -- rehearsed on this box's one GPU over gloo (PGR_BENCH_ONE_GPU=1: RCCL wants one GPU per rank): the line
     carries `ranks_joined`, the configs[4] leg (1e6 rays per rank, end records all-gathered, histogram all-reduced: every
     surviving ray counted once) and the sharded eigenray search; its whole-job value is steps x passes / wall."""
@@ -1369,7 +1369,7 @@ def test_bench_two_ranks_on_one_gpu_carries_the_multi_gpu_legs(lib):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, PGR_BENCH_ONE_GPU="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--backend", "gloo", "--steps", "2", "--warmup", "1",
-                        "--eigen-rays", "200000"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
+                        "--eigen-rays", "200000", "--full"], capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -1383,6 +1383,30 @@ def test_bench_two_ranks_on_one_gpu_carries_the_multi_gpu_legs(lib):
     es = d["eigenray_sharded"]
     assert es["ranks"] == 2 and es["found"] + es["failed"] == es["brackets"] and es["found"] > 10
     assert "cpu_baseline" not in d and "api" not in d.get("legs", {})      # rank-0-at-N=1-only legs stay out
+
+
+def test_bench_plain_run_measures_the_headline_alone(lib):
+    """`python bench.py` without --full: the headline line (value = steps x passes / wall, the roofline of the timed steps)
+    and nothing that takes runs of its own -- no CPU baselines, eigenray search, extra legs or lone wave."""
+    import json
+    import os
+    import subprocess
+    import sys
+    import bench
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    p = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1"],
+                       capture_output=True, text=True, timeout=300, cwd=root)
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, p.stdout[-2000:]
+    d = json.loads(lines[0])
+    assert d["metric"] == bench.BASELINE_METRIC and d["unit"] == "ray-steps/s" and d["higher_is_better"] is True
+    assert d["dtype"] == "f64" and d["n_gpus"] == 1 and d["steps"] == 2 and d["warmup"] == 1
+    assert abs(d["value"] - d["config"]["ray_steps_per_pass"] / (d["ms_per_step"] * 1e-3)) < 1e-6 * d["value"]
+    assert 1.4e8 < d["config"]["ray_steps_per_pass"] < 1.5e8 and len(d["roofline"]["kernel_ms_each"]) == 2
+    for key in ("cpu_baseline", "cpu_baseline_c", "eigenray", "eigenray_sharded", "legs", "lone_wave_ms"):
+        assert key not in d, key
+    assert "frac_rays_1e6_end_state" not in d["roofline"]
 
 
 def test_arrival_time_histogram_equals_numpy(lib):

@@ -862,6 +862,18 @@ def test_build_reports_that_the_layout_pass_was_applied():
     assert "correctly rounded div/sqrt/pow/asin/sin" in info and "NOT bit-identical" not in info
 
 
+def test_bench_runs_its_extra_legs_only_with_full():
+    """A plain `bench.py` run measures the headline alone; --full adds the CPU baselines, the eigenray search and the
+    extra legs, and the --no-* switches leave parts of --full out."""
+    import bench
+    plain = bench.parse_args(["--steps", "5", "--warmup", "1"])
+    assert not (plain.full or plain.cpu_baseline or plain.eigenray or plain.legs)
+    full = bench.parse_args(["--full"])
+    assert full.cpu_baseline and full.eigenray and full.legs
+    part = bench.parse_args(["--full", "--no-cpu-baseline", "--no-legs"])
+    assert part.eigenray and not part.cpu_baseline and not part.legs
+
+
 def test_bench_gpus_n_starts_n_ranks_itself():
     """`python bench.py --gpus N` run plainly launches N ranks (fresh children, one per GPU) before
     touching a GPU; rank 0 reports; a wrong external WORLD_SIZE is an error, not a silent 1-GPU run.
