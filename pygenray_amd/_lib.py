@@ -15,7 +15,10 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 REFERENCE_LIB = os.path.join(CSRC, "libpgr_hip.so")
 CONTRACTED_LIB = os.path.join(CSRC, "libpgr_hip_fma.so")
-CONTRACTED_FLAGS = ["-DPGR_FMA", "-ffp-contract=fast"]
+# fast-honor-pragmas: a*b + c fused everywhere EXCEPT where the source says `#pragma clang fp contract(off)` (grid_at,
+# pgr_device.h: the np.linspace / table coordinates the histogram and the look-ups must reproduce bit for bit); a direct
+# device compile with plain `fast` ignores the pragma (tests/test_host.py)
+CONTRACTED_FLAGS = ["-DPGR_FMA", "-ffp-contract=fast-honor-pragmas"]
 
 
 class PgrError(RuntimeError):
@@ -41,7 +44,8 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 # whose own constants never fitted anyway, gets up to 3 % faster.  (Three waves per SIMD then fit,
 # but measured slower: 1e6 rays 45.0 vs 42.4 ms, 180 000 rays 13.1 vs 9.8 ms -- a workgroup holds
 # its CU until its last wave ends and the fans are VALU-bound already.)
-# -ffp-contract=off: the reference's arithmetic (build_contracted() appends CONTRACTED_FLAGS, whose -ffp-contract=fast wins).
+# -ffp-contract=off: the reference's arithmetic (build_contracted() appends CONTRACTED_FLAGS, whose
+# -ffp-contract=fast-honor-pragmas wins: contraction everywhere but inside `#pragma clang fp contract(off)`).
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-mllvm", "-disable-machine-licm",
                "-ffp-contract=off"]
 

@@ -46,7 +46,8 @@ class Arrivals:
     - ``time``: T_k + w (T_k+1 - T_k), seconds
     - ``p``: p_k + w (p_k+1 - p_k), the slowness in ``RayFan.ps``'s sign convention
     - ``intensity``: the tube's term of ``transmission_loss(..., intensity=True)``; summed in order from 0.0 it gives that
-      value at (j, c) bit for bit
+      value at (j, c) bit for bit -- in either arithmetic, against that library's own TL (``PGR_ARITH=contracted``: the
+      counts, order and this sum are exact; the values are within a derived bound of the reference build's)
     - lazily: ``launch_angle`` (degrees, ``rays.thetas``' convention, interpolated by w), ``amplitude`` = sqrt(intensity),
       ``received_angle`` = degrees(arcsin(p c(x, D_j))) with c from the tables of the frame the fan was traced in
       (``host_physics.ray_angle``'s definition; ``EigenRays.received_angles`` uses the non-flat-earth table instead).

@@ -266,6 +266,11 @@ extern "C" int pgr_arrival_histogram_device(int device, const double* t_end, int
     if (nbins < 1 || nbins > 16384) return fail("pgr_arrival_histogram_device: nbins must be 1..16384");
     if (!(t_max > t_min) || !isfinite(t_min) || !isfinite(t_max))
         return fail("pgr_arrival_histogram_device: need finite t_min < t_max");
+    // np.histogram refuses a range whose np.linspace edges are not strictly increasing ("Too many bins for data range")
+    for (int32_t j = 0; j < nbins; j++)
+        if (!(linspace_at(t_min, t_max, nbins + 1, j) < linspace_at(t_min, t_max, nbins + 1, j + 1)))
+            return fail("pgr_arrival_histogram_device: the np.linspace edges of (t_min, t_max) are not strictly increasing "
+                        "for nbins = " + std::to_string(nbins) + " (too many bins for the data range)");
     HIPCHK(hipSetDevice(device));
     hipStream_t st = (hipStream_t)stream;
     HIPCHK(hipMemsetAsync(counts, 0, (size_t)nbins * 8, st));

@@ -127,6 +127,12 @@ def arrival_time_histogram(t_end, status, bins, t_min, t_max, group=None, reduce
         from . import _lib
         if t_end.dtype != torch.float64 or status.dtype != torch.int32 or t_end.dim() != 1 or status.dim() != 1:
             raise TypeError("arrival_time_histogram: need 1-D float64 times and int32 status")
+        import numpy as np
+        if float(t_min) < float(t_max) and 1 <= bins <= 16384:
+            # np.histogram's own refusal, so that both paths take the same ranges (the C entry checks it too)
+            edges = np.linspace(float(t_min), float(t_max), bins + 1)
+            if not (edges[:-1] < edges[1:]).all():
+                raise ValueError(f"Too many bins for data range. Cannot create {bins} finite-sized bins.")
         n = t_end.shape[0]
         h = torch.empty(bins, dtype=torch.int64, device=t_end.device)
         _lib.arrival_histogram_device(t_end.device.index or 0, t_end.data_ptr(), t_end.stride(0) if n else 1,

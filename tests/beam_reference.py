@@ -31,6 +31,29 @@ def gexp(y):
     return np.ldexp(p, k.astype(np.int64))
 
 
+def _fma(a, b, c):
+    """a * b + c rounded once (Fraction -> float is correctly rounded)"""
+    from fractions import Fraction
+    return float(Fraction(a) * Fraction(b) + Fraction(c))
+
+
+def gexp_contracted(y):
+    """gexp of one y as the contracted library computes it: every a * b + c of gexp fused (-ffp-contract=fast-honor-pragmas)."""
+    y = float(y)
+    k = float(np.rint(y * _LOG2E))
+    r = _fma(-k, _LN2_LO, _fma(-k, _LN2_HI, y))
+    p = _TAYLOR[0]
+    for c in _TAYLOR[1:]:
+        p = _fma(p, r, c)
+    return math.ldexp(p, int(k))
+
+
+# the worst errors of gexp and gexp_contracted against exp on test_beam_tl_host.py's [-8, 0] sample set, in ulps of exp, as
+# measured there (0.84 for the contracted one): tests/test_contracted_arith.py bounds the beams' values with them
+GEXP_ULPS = 1.5
+GEXP_CONTRACTED_ULPS = 0.84
+
+
 def frame_tables(x, environment, flatearth=True):
     """The tables of the frame a fan with save ranges x was traced in -> (x in that frame, cin, rin, zin, depths,
     depth_ranges): mirrored, x -> -x, for a backwards fan."""
@@ -71,7 +94,7 @@ def _tubes(zs, ps, x, p0, cin, rin, zin, w_min):
     return valid, m, sigma, E, A, r
 
 
-def beam_intensity(zs, ps, x, p0, depths, cin, rin, zin, bottom, w_min):
+def beam_intensity(zs, ps, x, p0, depths, cin, rin, zin, bottom, w_min, a_scale=None):
     """The definition, restated: zs / ps (M, S) stored convention (depth = -z), x (S,) save ranges in the frame of the tables,
     p0 (M,) launch slowness, bottom (S,) bottom depths in that frame -> I (len(depths), S).
 
@@ -80,6 +103,8 @@ def beam_intensity(zs, ps, x, p0, depths, cin, rin, zin, bottom, w_min):
     depths = np.asarray(depths, dtype=float)
     bottom = np.asarray(bottom, dtype=float)
     valid, m, sigma, E, A, r = _tubes(zs, ps, x, p0, cin, rin, zin, w_min)
+    if a_scale is not None:                              # (M-1, S): every term of tube k scaled (error bounds)
+        A = A * a_scale
     R, S = len(depths), len(r)
     order = np.argsort(depths, kind="stable")
     ds = depths[order]

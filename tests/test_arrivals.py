@@ -7,8 +7,8 @@ import pytest
 import arrivals_reference as ar
 import tl_reference as tlr
 from test_arrivals_host import check_gradient_arrivals
-from tube_gpu import (DEPTHS, SYN_R, SYN_Z, _device_arrivals, _env, munk_env, pr, sloping_env,  # noqa: F401
-                      sloping_env_shallow_table, syn_env, synthetic_fan)  # (pr, syn_env: fixtures)
+from tube_gpu import (DEPTHS, SYN_R, SYN_Z, _device_arrivals, _env, munk_env, pr, pr_any, sloping_env,  # noqa: F401
+                      sloping_env_shallow_table, syn_env, synthetic_fan)  # (pr, pr_any, syn_env: fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -181,16 +181,16 @@ def test_flatearth_host_fan(pr):
 
 # ---- closed forms end to end -------------------------------------------------------------------------------------------
 
-def test_isovelocity_fan_gives_one_arrival_per_image_source(pr):
+def test_isovelocity_fan_gives_one_arrival_per_image_source(pr_any):
     z = np.arange(0, 6000, 10.0)
     r = np.linspace(0, 25e3, 6)
-    env = _env(pr, z, r, np.full((len(r), len(z)), 1500.0), r, np.full(len(r), 5000.0))
-    fan = pr.shoot_rays(1000.0, 0.0, np.linspace(-80, 80, 20001), 20e3, 2001, env, flatearth=False, debug=False)
+    env = _env(pr_any, z, r, np.full((len(r), len(z)), 1500.0), r, np.full(len(r), 5000.0))
+    fan = pr_any.shoot_rays(1000.0, 0.0, np.linspace(-80, 80, 20001), 20e3, 2001, env, flatearth=False, debug=False)
     assert len(fan) == 20001 and fan.device_resident
     depths = np.arange(tlr.MARGIN, 5000 - tlr.MARGIN + 1, 50.0)
     x = np.asarray(fan.rs[0])
     cols = np.nonzero((x >= 1e3) & (x <= 20e3))[0][::10]
-    a = pr.arrivals(fan, depths, env, flatearth=False, range_indices=cols)
+    a = pr_any.arrivals(fan, depths, env, flatearth=False, range_indices=cols)
     assert fan.device_resident
     zs, ps = np.asarray(fan.zs), np.asarray(fan.ps)
     n, spacing = len(cols), 160.0 / 20000
@@ -220,14 +220,14 @@ def test_isovelocity_fan_gives_one_arrival_per_image_source(pr):
 
 
 @pytest.mark.parametrize("device_resident", [True, False])
-def test_linear_gradient_fan_matches_the_closed_form(pr, device_resident):
+def test_linear_gradient_fan_matches_the_closed_form(pr_any, device_resident):
     env = tlr.gradient_env()
-    fan = pr.shoot_rays(tlr.GRADIENT_ZS, 0.0, np.linspace(-tlr.GRADIENT_APERTURE, tlr.GRADIENT_APERTURE, 2001),
+    fan = pr_any.shoot_rays(tlr.GRADIENT_ZS, 0.0, np.linspace(-tlr.GRADIENT_APERTURE, tlr.GRADIENT_APERTURE, 2001),
                         tlr.GRADIENT_X1, tlr.GRADIENT_S, env, flatearth=False, debug=False, device_resident=device_resident)
     x = np.asarray(fan.rs[0])
     cols = np.nonzero(x >= 1e3)[0]
-    a = pr.arrivals(fan, tlr.GRADIENT_DEPTHS, env, flatearth=False, range_indices=cols)
-    I = pr.transmission_loss(fan, tlr.GRADIENT_DEPTHS, env, flatearth=False, intensity=True)
+    a = pr_any.arrivals(fan, tlr.GRADIENT_DEPTHS, env, flatearth=False, range_indices=cols)
+    I = pr_any.transmission_loss(fan, tlr.GRADIENT_DEPTHS, env, flatearth=False, intensity=True)
     assert fan.device_resident == device_resident
     c_s = tlr.GRADIENT_CA + tlr.GRADIENT_GAMMA * tlr.GRADIENT_ZS
     theta0 = np.arcsin(-np.asarray(fan.ps)[:, 0] * c_s)       # depth-down, from the fan itself (as the TL test)
@@ -279,14 +279,14 @@ def test_last_column_tubes_are_the_eigenray_brackets(pr):
 
 # ---- headline scale ----------------------------------------------------------------------------------------------------
 
-def test_headline_fan_twice_bit_equal(pr):
-    env = pr.OceanEnvironment2D()
-    fan = pr.shoot_rays(1000.0, 0.0, np.linspace(-20, 20, 100_000), 100e3, 1001, env, debug=False)
+def test_headline_fan_twice_bit_equal(pr_any):
+    env = pr_any.OceanEnvironment2D()
+    fan = pr_any.shoot_rays(1000.0, 0.0, np.linspace(-20, 20, 100_000), 100e3, 1001, env, debug=False)
     assert fan.device_resident and len(fan) > 90_000
-    I_tl = pr.transmission_loss(fan, DEPTHS, env, intensity=True)
+    I_tl = pr_any.transmission_loss(fan, DEPTHS, env, intensity=True)
     for cols in (None, np.arange(0, 1001, 50)):
-        a = pr.arrivals(fan, DEPTHS, env, range_indices=cols)
-        b = pr.arrivals(fan, DEPTHS, env, range_indices=cols)
+        a = pr_any.arrivals(fan, DEPTHS, env, range_indices=cols)
+        b = pr_any.arrivals(fan, DEPTHS, env, range_indices=cols)
         assert fan.device_resident and "_zs" not in fan.__dict__
         assert _same_arrivals(a, b)
         _check_sum_identity(a, I_tl)

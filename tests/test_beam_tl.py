@@ -10,8 +10,8 @@ import beam_reference as bref
 import tl_reference as tlr
 from pygenray_amd.host_physics import bilinear_interp
 from pygenray_amd.launch_rays import _initial_slowness
-from tube_gpu import (SYN_R, SYN_Z, _device_beams, _env, _same, munk_env, pr, sloping_env,  # noqa: F401
-                      sloping_env_shallow_table, syn_env, synthetic_fan)  # (pr, syn_env: fixtures)
+from tube_gpu import (SYN_R, SYN_Z, _device_beams, _env, _same, munk_env, pr, pr_any, sloping_env,  # noqa: F401
+                      sloping_env_shallow_table, syn_env, synthetic_fan)  # (pr, pr_any, syn_env: fixtures)
 
 pytestmark = pytest.mark.gpu
 
@@ -137,13 +137,13 @@ def test_one_answer_from_the_device_and_host_paths(pr, case):
     assert np.isnan(a[:, 0]).all() and (a[:, 1:] > 0).mean() > 0.3
 
 
-def test_headline_fan_twice_bit_equal(pr):
-    env = pr.OceanEnvironment2D()
-    fan = pr.shoot_rays(1000.0, 0.0, np.linspace(-20, 20, 100_000), 100e3, 1001, env, debug=False)
+def test_headline_fan_twice_bit_equal(pr_any):
+    env = pr_any.OceanEnvironment2D()
+    fan = pr_any.shoot_rays(1000.0, 0.0, np.linspace(-20, 20, 100_000), 100e3, 1001, env, debug=False)
     assert fan.device_resident
     depths = np.linspace(0.0, 5000.0, 1000)
-    a = pr.beam_transmission_loss(fan, depths, env, intensity=True)
-    b = pr.beam_transmission_loss(fan, depths, env, intensity=True)
+    a = pr_any.beam_transmission_loss(fan, depths, env, intensity=True)
+    b = pr_any.beam_transmission_loss(fan, depths, env, intensity=True)
     assert fan.device_resident and a.shape == (1000, 1001)
     assert _same(a, b) and (a[:, 1:] > 0).mean() > 0.3
 
@@ -185,14 +185,14 @@ def test_the_c_entries_refuse_a_bad_min_width_and_write_nothing(pr, syn_env, w):
 
 # ---- physics on HIP fans ------------------------------------------------------------------------------------------------
 
-def test_isovelocity_fan_end_to_end_matches_the_image_sum(pr):
+def test_isovelocity_fan_end_to_end_matches_the_image_sum(pr_any):
     z = np.arange(0, 6000, 10.0)
     r = np.linspace(0, 25e3, 6)
-    env = _env(pr, z, r, np.full((len(r), len(z)), 1500.0), r, np.full(len(r), 5000.0))
-    fan = pr.shoot_rays(1000.0, 0.0, np.linspace(-80, 80, 20001), 20e3, 2001, env, flatearth=False, debug=False)
+    env = _env(pr_any, z, r, np.full((len(r), len(z)), 1500.0), r, np.full(len(r), 5000.0))
+    fan = pr_any.shoot_rays(1000.0, 0.0, np.linspace(-80, 80, 20001), 20e3, 2001, env, flatearth=False, debug=False)
     assert len(fan) == 20001 and fan.device_resident
     depths = np.arange(tlr.MARGIN, 5000 - tlr.MARGIN + 1, 50.0)
-    tl = pr.beam_transmission_loss(fan, depths, env, flatearth=False)
+    tl = pr_any.beam_transmission_loss(fan, depths, env, flatearth=False)
     x = np.asarray(fan.rs[0])
     assert np.isnan(tl[:, 0]).all()
     keep = (x >= 1e3) & (x <= 20e3)
@@ -204,16 +204,16 @@ def test_isovelocity_fan_end_to_end_matches_the_image_sum(pr):
     assert err.max() < tlr.TOL_DB, (err.max(), depths[j], x[keep][k])
 
 
-def test_energy_identity_on_a_munk_fan(pr):
+def test_energy_identity_on_a_munk_fan(pr_any):
     # at a few columns, the trapezoid integral of the kernel's intensity over [0, b] on a grid of w_min / 8 is the sum of
     # the beams' energies times their masses inside the column (tests/test_beam_tl_host.py derives the bound)
-    env = munk_env(pr)
+    env = munk_env(pr_any)
     w_min = 10.0
-    fan = pr.shoot_rays(1000.0, 0.0, np.linspace(-20, 20, 2000), 60e3, 61, env, flatearth=False, debug=False)
+    fan = pr_any.shoot_rays(1000.0, 0.0, np.linspace(-20, 20, 2000), 60e3, 61, env, flatearth=False, debug=False)
     H = 5000.0
     depths = np.linspace(0.0, H, int(math.ceil(H / (w_min / 8))) + 1)
     h = depths[1] - depths[0]
-    I = pr.beam_transmission_loss(fan, depths, env, flatearth=False, intensity=True, min_width=w_min)
+    I = pr_any.beam_transmission_loss(fan, depths, env, flatearth=False, intensity=True, min_width=w_min)
     cols = np.array([0, 7, 30, 60])
     xf, cin, rin, zin, bd, br = bref.frame_tables(np.asarray(fan.rs[0]), env, flatearth=False)
     p0 = _initial_slowness(fan.thetas, bilinear_interp(xf[0], 1000.0, rin, zin, cin))

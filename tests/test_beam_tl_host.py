@@ -18,19 +18,37 @@ ISO_CIN = np.full((2, 3), C0)
 ISO_RIN, ISO_ZIN = np.array([-1.0, 30e3]), np.array([0.0, 3000.0, 6000.0])
 
 
-def test_gexp_is_within_one_and_a_half_ulp_of_exp():
-    import mpmath
-    mpmath.mp.dps = 40
+def _gexp_samples():
     y = np.concatenate([np.linspace(-8.0, 0.0, 20001), -np.random.default_rng(5).uniform(0.0, 8.0, 2000),
                         [np.nextafter(-8.0, 0.0), -0.0, -1e-300, -np.log(2) / 2, np.log(2) / 2 - 1.0]])
     assert y.min() == -8.0 and y.max() == 0.0
+    return y
+
+
+def test_gexp_is_within_one_and_a_half_ulp_of_exp():
+    import mpmath
+    mpmath.mp.dps = 40
+    y = _gexp_samples()
     g = bref.gexp(y)
     worst = 0.0
     for a, b in zip(y, g):
         e = mpmath.exp(mpmath.mpf(float(a)))
         worst = max(worst, abs(float((mpmath.mpf(float(b)) - e) / np.spacing(float(e)))))
-    assert worst <= 1.5, worst
+    assert worst <= bref.GEXP_ULPS, worst
     assert bref.gexp(0.0) == 1.0
+
+
+def test_contracted_gexp_error_is_the_one_the_contracted_beam_bound_uses():
+    # gexp with every a * b + c fused (the contracted library) on the same samples: the measured worst error is
+    # bref.GEXP_CONTRACTED_ULPS, which tests/test_contracted_arith.py puts into its bound on the beams' values
+    import mpmath
+    mpmath.mp.dps = 40
+    worst = 0.0
+    for a in _gexp_samples():
+        e = mpmath.exp(mpmath.mpf(float(a)))
+        worst = max(worst, abs(float((mpmath.mpf(bref.gexp_contracted(a)) - e) / np.spacing(float(e)))))
+    assert 0.5 < worst <= bref.GEXP_CONTRACTED_ULPS, worst
+    assert bref.gexp_contracted(0.0) == 1.0
 
 
 def test_restatement_matches_the_image_sum_in_an_isovelocity_waveguide():

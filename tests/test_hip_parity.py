@@ -7,6 +7,7 @@ and the drop-in API on top of it.
 import numpy as np
 import pytest
 
+import hist_cases
 import oracle
 from helpers import (load, env_from, tiled_env, munk, munk_arrays, y0_for, assert_fan_parity,
                      assert_bit_parity, oracle_selfnoise, random_case, XI_MAX, NOISE_FACTOR)
@@ -1445,6 +1446,41 @@ def test_arrival_time_histogram_equals_numpy(lib):
         arrival_time_histogram(end[:, 0], std, 16, hi, lo)
     with pytest.raises(lib.PgrError):
         arrival_time_histogram(end[:, 0], std, 100_000, lo, hi)
+
+
+@pytest.mark.parametrize("name, t_min, t_max, bins, min_mismatches", hist_cases.RANGES,
+                         ids=[r[0] for r in hist_cases.RANGES])
+def test_arrival_time_histogram_on_every_edge(lib, name, t_min, t_max, bins, min_mismatches):
+    """np.histogram's bin rule on ranges whose np.linspace edges are inexact: values on every edge and one ulp either side,
+    the range ends and their outer neighbours, NaN, dropped rays on edges (tests/hist_cases.py)."""
+    hist_cases.check_device_histogram(t_min, t_max, bins, min_mismatches)
+
+
+def test_arrival_time_histogram_refuses_what_numpy_refuses(lib):
+    """A range too narrow for its bins (np.linspace's edges not strictly increasing) raises ValueError on the device path,
+    as np.histogram does on the host path; the C entry refuses it and writes nothing.  The near-degenerate range that
+    NumPy still takes is taken."""
+    import torch
+    from pygenray_amd.distributed import arrival_time_histogram
+    lo, hi, bins = hist_cases.DEGENERATE
+    t = torch.full((1000,), lo, dtype=torch.float64)
+    st = torch.zeros(1000, dtype=torch.int32)
+    with pytest.raises(ValueError, match="Too many bins"):
+        arrival_time_histogram(t, st, bins, lo, hi)
+    with pytest.raises(ValueError, match="Too many bins"):
+        arrival_time_histogram(t.cuda(), st.cuda(), bins, lo, hi)
+    counts = torch.full((bins,), -7, dtype=torch.int64, device="cuda")
+    with pytest.raises(lib.PgrError, match="strictly increasing"):
+        lib.arrival_histogram_device(0, t.cuda().data_ptr(), 1, st.cuda().data_ptr(), 1, 1000, lo, hi, bins, counts.data_ptr())
+    torch.cuda.synchronize()
+    assert (counts.cpu() == -7).all()
+    name, lo, hi, bins, _ = hist_cases.RANGES[-1]
+    assert name == "near-degenerate"
+    tt = torch.from_numpy(np.linspace(lo, hi, bins + 1))
+    ss = torch.zeros(bins + 1, dtype=torch.int32)
+    want = arrival_time_histogram(tt, ss, bins, lo, hi)
+    assert np.array_equal(arrival_time_histogram(tt.cuda(), ss.cuda(), bins, lo, hi).cpu().numpy(), want.numpy())
+    assert int(want.sum()) == bins + 1
 
 
 def test_wave_scheduler_is_a_pure_permutation(lib):

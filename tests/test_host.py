@@ -812,6 +812,31 @@ def test_device_code_hash_reads_the_built_library():
     h = _lib.device_code_sha256()
     assert len(h) == 64 and h == _lib.device_code_sha256(_lib.LIB_PATH)
 
+
+def test_contracted_flags_honour_the_no_contraction_pragma(tmp_path):
+    """The contracted library fuses a*b + c everywhere except inside `#pragma clang fp contract(off)` (grid_at: the
+    np.linspace edges of the histogram, the table coordinates).  Plain -ffp-contract=fast ignores that pragma; the flags
+    the contracted build uses must not.  Device-only assembly of a kernel that has the pragma, and one that has not."""
+    from pygenray_amd import _lib
+    if not os.path.exists(_lib.HIPCC):
+        pytest.skip("hipcc not installed")
+    src = tmp_path / "k.hip"
+    src.write_text("#include <hip/hip_runtime.h>\n"
+                   "__global__ void kept(double* o, const double* a, int j)\n"
+                   "{\n#pragma clang fp contract(off)\n    double m = (double)j * a[1];\n    o[0] = a[0] + m;\n}\n"
+                   "__global__ void fused(double* o, const double* a, int j)\n"
+                   "{\n    double m = (double)j * a[1];\n    o[0] = a[0] + m;\n}\n")
+    flags = [f for f in _lib.HIPCC_FLAGS + _lib.CONTRACTED_FLAGS if f not in ("-shared", "-fPIC")]
+    subprocess.check_call([_lib.HIPCC] + flags + ["--cuda-device-only", "-S", "-o", str(tmp_path / "k.s"), str(src)],
+                          cwd=tmp_path)
+    asm = (tmp_path / "k.s").read_text()
+    bodies = {}
+    for name in ("kept", "fused"):
+        sym = re.search(r"^(_Z\d+%s\w*):" % name, asm, re.M).group(1)
+        bodies[name] = asm[asm.index(sym + ":"):asm.index(".Lfunc_end", asm.index(sym + ":"))]
+    assert not re.search(r"v_fmac?_f64", bodies["kept"]) and "v_mul_f64" in bodies["kept"], bodies["kept"]
+    assert re.search(r"v_fmac?_f64", bodies["fused"]), bodies["fused"]    # (the flags do contract elsewhere)
+
 # ----------------------------------------------------------------------------- build: instruction layout
 def test_instruction_layout_pass_plans_encodings():
     """pygenray_amd/_isa_layout.py: 4-byte e32 VALU instructions are re-encoded as 8-byte e64 ones

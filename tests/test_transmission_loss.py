@@ -5,23 +5,23 @@ import numpy as np
 import pytest
 
 import tl_reference as tlr
-from tube_gpu import (DEPTHS, SYN_R, SYN_Z, _device_intensity, _env, _same, munk_env, pr, sloping_env,  # noqa: F401
-                      sloping_env_shallow_table, syn_env, synthetic_fan)  # (pr, syn_env: fixtures)
+from tube_gpu import (DEPTHS, SYN_R, SYN_Z, _device_intensity, _env, _same, munk_env, pr, pr_any, sloping_env,  # noqa: F401
+                      sloping_env_shallow_table, syn_env, synthetic_fan)  # (pr, pr_any, syn_env: fixtures)
 
 pytestmark = pytest.mark.gpu
 
 
-def test_isovelocity_fan_end_to_end_matches_the_image_sum(pr):
+def test_isovelocity_fan_end_to_end_matches_the_image_sum(pr_any):
     z = np.arange(0, 6000, 10.0)
     r = np.linspace(0, 25e3, 6)
-    env = _env(pr, z, r, np.full((len(r), len(z)), 1500.0), r, np.full(len(r), 5000.0))
+    env = _env(pr_any, z, r, np.full((len(r), len(z)), 1500.0), r, np.full(len(r), 5000.0))
     # 10 m between save ranges: a sample next to a reflection may come from the reflected segment's dense output evaluated
     # up to half a sample spacing before the reflection (the reference's nearest-index re-sampling), i.e. up to
     # 5 m x tan(80 deg) = 28 m outside the water column -- inside the receivers' margin
-    fan = pr.shoot_rays(1000.0, 0.0, np.linspace(-80, 80, 20001), 20e3, 2001, env, flatearth=False, debug=False)
+    fan = pr_any.shoot_rays(1000.0, 0.0, np.linspace(-80, 80, 20001), 20e3, 2001, env, flatearth=False, debug=False)
     assert len(fan) == 20001 and fan.device_resident
     depths = np.arange(tlr.MARGIN, 5000 - tlr.MARGIN + 1, 50.0)
-    tl = pr.transmission_loss(fan, depths, env, flatearth=False)
+    tl = pr_any.transmission_loss(fan, depths, env, flatearth=False)
     x = np.asarray(fan.rs[0])
     assert np.isnan(tl[:, 0]).all()
     keep = (x >= 1e3) & (x <= 20e3)
@@ -65,12 +65,12 @@ def test_one_answer_whatever_the_path(pr):
     assert _same(a, pr.transmission_loss(dev, DEPTHS, env, flatearth=False))
 
 
-def test_headline_fan_twice_bit_equal(pr):
-    env = pr.OceanEnvironment2D()
-    fan = pr.shoot_rays(1000.0, 0.0, np.linspace(-20, 20, 100_000), 100e3, 1001, env, debug=False)
+def test_headline_fan_twice_bit_equal(pr_any):
+    env = pr_any.OceanEnvironment2D()
+    fan = pr_any.shoot_rays(1000.0, 0.0, np.linspace(-20, 20, 100_000), 100e3, 1001, env, debug=False)
     assert fan.device_resident
-    a = pr.transmission_loss(fan, DEPTHS, env, intensity=True)
-    b = pr.transmission_loss(fan, DEPTHS, env, intensity=True)
+    a = pr_any.transmission_loss(fan, DEPTHS, env, intensity=True)
+    b = pr_any.transmission_loss(fan, DEPTHS, env, intensity=True)
     assert fan.device_resident and a.shape == (1000, 1001)
     assert _same(a, b) and (a[:, 1:] > 0).mean() > 0.3
 
@@ -220,12 +220,12 @@ def test_flatearth_host_fan(pr):
 # ---- a refracting medium: the HIP fan and TL against the linear-gradient closed form ------------------------------------
 
 @pytest.mark.parametrize("device_resident", [True, False])
-def test_linear_gradient_fan_matches_the_closed_form(pr, device_resident):
+def test_linear_gradient_fan_matches_the_closed_form(pr_any, device_resident):
     env = tlr.gradient_env()
-    fan = pr.shoot_rays(tlr.GRADIENT_ZS, 0.0, np.linspace(-tlr.GRADIENT_APERTURE, tlr.GRADIENT_APERTURE, 2001),
+    fan = pr_any.shoot_rays(tlr.GRADIENT_ZS, 0.0, np.linspace(-tlr.GRADIENT_APERTURE, tlr.GRADIENT_APERTURE, 2001),
                         tlr.GRADIENT_X1, tlr.GRADIENT_S, env, flatearth=False, debug=False, device_resident=device_resident)
     assert len(fan) == 2001 and fan.device_resident == device_resident
-    I = pr.transmission_loss(fan, tlr.GRADIENT_DEPTHS, env, flatearth=False, intensity=True)
+    I = pr_any.transmission_loss(fan, tlr.GRADIENT_DEPTHS, env, flatearth=False, intensity=True)
     # the depth-down launch angle from the fan itself (stored p = -sin(theta0) / c_s), not from the user angles (Q1)
     c_s = tlr.GRADIENT_CA + tlr.GRADIENT_GAMMA * tlr.GRADIENT_ZS
     theta0 = np.arcsin(-np.asarray(fan.ps)[:, 0] * c_s)

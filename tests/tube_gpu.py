@@ -1,5 +1,5 @@
 """Shared scaffolding of the ray-tube GPU tests (test_transmission_loss.py, test_arrivals.py, test_beam_tl.py): the `pr`
-fixture, the environments, the synthetic fans aimed at the kernels' chunk, band and adds-nothing edges, and the helpers
+and `pr_any` fixtures, the environments, the synthetic fans aimed at the kernels' chunk, band and adds-nothing edges, and the helpers
 that upload caller buffers and call the `_device` entries.  Not a test module itself."""
 import numpy as np
 import pytest
@@ -9,9 +9,21 @@ import tl_reference as tlr
 
 @pytest.fixture(scope="module")
 def pr():
+    """the package, for the bit-parity tests: reference arithmetic only"""
     from pygenray_amd import _lib
     if _lib.ARITH != "reference":
         pytest.skip("bit parity is claimed for the reference arithmetic only (PGR_ARITH=contracted: tests/test_contracted_arith.py)")
+    _lib.load()
+    assert _lib.device_count() >= 1
+    import pygenray_amd
+    return pygenray_amd
+
+
+@pytest.fixture(scope="module")
+def pr_any():
+    """the package in whichever arithmetic this process loaded, for the tolerance tests (closed forms, repeatability): they
+    also run in the PGR_ARITH=contracted child of tests/test_contracted_arith.py"""
+    from pygenray_amd import _lib
     _lib.load()
     assert _lib.device_count() >= 1
     import pygenray_amd
@@ -57,7 +69,7 @@ SYN_Z = np.concatenate([np.arange(0.0, 1000.0, 20.0), np.arange(1000.0, 5001.0, 
 
 
 @pytest.fixture(scope="module")
-def syn_env(pr):
+def syn_env(pr_any):
     """a small range-dependent table (tables in HBM): smooth, positive, so that the bilinear look-up of c matters"""
     from pygenray_amd import _lib
     rr, zz = np.meshgrid(SYN_R, SYN_Z, indexing="ij")
