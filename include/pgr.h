@@ -323,6 +323,34 @@ int pgr_beam_intensity_device(pgr_env* env, const double* z, const double* p, in
                               const double* x, const double* p0, const double* bottom, const double* depths,
                               int64_t n_depths, double min_width, double* out, void* stream);
 
+/* Travel-time sensitivity kernel of a fan on a range-depth grid ("Travel-time sensitivity kernels"): the linear
+ * map dT = K . dc from a sound-speed perturbation on the grid ranges[n_ranges] x depths[n_depths] to the travel times of
+ * the surviving rays at save column `column`.  Per ray m (depth d = -z, travel time T, save ranges x), the path is the
+ * polyline through samples 0 ... column; chord s -> s + 1 is cut at every interior grid line it crosses strictly inside,
+ * and each piece (length l, in the grid cell it lies in) adds, by Simpson's rule at its ends and midpoint,
+ *   Q_ab(s) += l/6 [f(0) + 4 f(1/2) + f(1)],  f = phi_ab / c^2,       Q_1(s) += l/6 [g(0) + 4 g(1/2) + g(1)],  g = 1 / c,
+ * phi_ab the bilinear weight of node (a, b) (host_physics.bilinear_interp: clamped cell, unclamped weights), c the
+ * look-up of pgr_fan_intensity.  Then
+ *   out[(m * n_ranges + a) * n_depths + b] = sum over s < column, in increasing s from 0.0, of
+ *                                            - beta_s Q_ab(s),   beta_s = (T(s+1) - T(s)) / Q_1(s)  (0 if Q_1 == 0),
+ * in s / (m/s).  A NaN in T or z at samples 0 ... column makes row m all NaN; column 0 gives zeros.  Divisions and the
+ * square root correctly rounded, nothing contracted (reference build).  Every entry is written (zeros included); no
+ * atomics: one lane forms each entry in the order above, so repeated calls are bit-equal.
+ *
+ * ranges[n_ranges], depths[n_depths] (DEVICE): strictly ascending, 2 <= n_ranges <= 65535, 2 <= n_depths <= 2^30; the
+ * ranges in the frame the fan was traced in (mirrored, x -> -x and reversed, for a backwards fan).  out (DEVICE)
+ * [M][n_ranges][n_depths] float64.  0 <= column < n_samples.
+ * pgr_fan_travel_time_kernel: a device-resident fan with the fan arguments, waiting and streams of pgr_fan_intensity
+ *   (either trajectory layout, dropped rays skipped through the keep list); M = its surviving rays, at least 1.
+ * pgr_travel_time_kernel_device: caller buffers T, z (DEVICE) [n_samples][n_rays] rows, stored sign convention, every ray
+ *   kept (M = n_rays, at most 2^24), x[n_samples] (DEVICE) the save ranges in the frame of `env`.  Enqueued on `stream`,
+ *   returns without synchronising. */
+int pgr_fan_travel_time_kernel(pgr_fan* fan, const double* ranges, int32_t n_ranges, const double* depths, int32_t n_depths,
+                               int32_t column, double* out, void* stream);
+int pgr_travel_time_kernel_device(pgr_env* env, const double* T, const double* z, int64_t n_rays, int32_t n_samples,
+                                  const double* x, const double* ranges, int32_t n_ranges, const double* depths,
+                                  int32_t n_depths, int32_t column, double* out, void* stream);
+
 /* Tuning options of ONE environment (per-ray results never depend on them; there is no process-wide
  * state: host threads that drive different GPUs hold different environments).
  *   PGR_OPT_WAVES_PER_BLOCK  a = waves (of 64 rays) per workgroup, 0 = automatic

@@ -13,6 +13,7 @@ from .launch_rays import shoot_rays, shoot_ray, _unpack_envi
 from .eigenrays import find_eigenrays
 from .transmission import transmission_loss, beam_transmission_loss
 from .arrivals import arrivals, Arrivals
+from .sensitivity import travel_time_kernel
 from .host_physics import (derivsrd, bottom_bounce, surface_bounce, ray_bounding_box_event,
                            ray_angle, bilinear_interp, linear_interp, vertical_ray)
 from . import _lib
@@ -22,6 +23,7 @@ from . import _lib
 ARITHMETIC = _lib.ARITH
 
 __all__ = ["OceanEnvironment2D", "munk_ssp", "eflat", "eflatinv", "flat_earth_c", "DataArray", "Ray", "RayFan",
-           "EigenRays", "shoot_rays", "shoot_ray", "find_eigenrays", "transmission_loss", "beam_transmission_loss", "arrivals", "Arrivals", "derivsrd", "bottom_bounce",
+           "EigenRays", "shoot_rays", "shoot_ray", "find_eigenrays", "transmission_loss", "beam_transmission_loss", "arrivals", "Arrivals",
+           "travel_time_kernel", "derivsrd", "bottom_bounce",
            "surface_bounce", "ray_bounding_box_event", "ray_angle", "bilinear_interp",
            "linear_interp", "vertical_ray"]

@@ -247,7 +247,10 @@ def load():
             ("pgr_intensity_device", [_vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _i64, _vp, _vp]),
             ("pgr_beam_intensity_device", [_vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _vp, _i64, f64, _vp, _vp]),
             ("pgr_arrival_counts_device", [_vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _i64, _vp, i32, _vp, _vp]),
-            ("pgr_arrivals_device", [_vp, _vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _i64, _vp, i32, _vp, _i64] + [_vp] * 6)):
+            ("pgr_arrivals_device", [_vp, _vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _i64, _vp, i32, _vp, _i64] + [_vp] * 6),
+            # the travel-time sensitivity kernel (csrc/pgr_sens.h): a per-ray product, same pair of entries
+            ("pgr_fan_travel_time_kernel", [_vp, _vp, i32, _vp, i32, i32, _vp, _vp]),
+            ("pgr_travel_time_kernel_device", [_vp, _vp, _vp, _i64, i32, _vp, _vp, i32, _vp, i32, i32, _vp, _vp])):
         getattr(L, name).restype = ctypes.c_int
         getattr(L, name).argtypes = argtypes
     _lib = L
@@ -559,6 +562,12 @@ class FanHandle:
                                       _vp(offsets_ptr), int(n_arrivals), _vp(tube_ptr), _vp(w_ptr), _vp(t_ptr), _vp(p_ptr),
                                       _vp(i_ptr), _vp(stream or None)))
 
+    def travel_time_kernel(self, ranges_ptr, n_ranges, depths_ptr, n_depths, column, out_ptr, stream=0):
+        """pgr_fan_travel_time_kernel on raw device pointers (ints): out[M][n_ranges][n_depths] = the travel-time sensitivity
+        kernel of this fan's surviving rays at save column `column` on the grid ranges x depths (include/pgr.h)."""
+        check(load().pgr_fan_travel_time_kernel(self._h, _vp(ranges_ptr), int(n_ranges), _vp(depths_ptr), int(n_depths),
+                                                int(column), _vp(out_ptr), _vp(stream or None)))
+
     def close(self):
         if getattr(self, "_h", None):
             load().pgr_fan_destroy(self._h)
@@ -683,3 +692,12 @@ def arrivals_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, 
                                      _vp(x_ptr), _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vptr(c), len(c),
                                      _vp(offsets_ptr), int(n_arrivals), _vp(tube_ptr), _vp(w_ptr), _vp(t_out_ptr),
                                      _vp(p_out_ptr), _vp(i_ptr), _vp(stream or None)))
+
+
+def travel_time_kernel_device(env, t_ptr, z_ptr, n_rays, n_samples, x_ptr, ranges_ptr, n_ranges, depths_ptr, n_depths,
+                              column, out_ptr, stream=0):
+    """pgr_travel_time_kernel_device on raw device pointers (ints): the travel-time sensitivity kernel of caller buffers
+    T / z [n_samples][n_rays] (stored sign convention) on `env` (an EnvHandle); see include/pgr.h."""
+    check(load().pgr_travel_time_kernel_device(env._h, _vp(t_ptr), _vp(z_ptr), int(n_rays), int(n_samples), _vp(x_ptr),
+                                               _vp(ranges_ptr), int(n_ranges), _vp(depths_ptr), int(n_depths), int(column),
+                                               _vp(out_ptr), _vp(stream or None)))

@@ -55,3 +55,4 @@
 #include "pgr_tl.h"             // ray-tube intensity / transmission loss: pgr_fan_intensity, pgr_intensity_device
 #include "pgr_arrivals.h"       // ray-tube arrivals at receiver depths: pgr_fan_arrival_counts, pgr_fan_arrivals, ..._device
 #include "pgr_beams.h"          // Gaussian-beam intensity: pgr_fan_beam_intensity, pgr_beam_intensity_device
+#include "pgr_sens.h"           // travel-time sensitivity kernels: pgr_fan_travel_time_kernel, pgr_travel_time_kernel_device

@@ -283,20 +283,18 @@ static int tl_check(int64_t M, int32_t S, const double* p0, const double* depths
     return 0;
 }
 
-// The prologue of the entries on a fan handle: a fan with trajectories; under its lock, once its kernel has finished (its M
-// is known then), tl_check and the entry's own check(S); the keep list and the save ranges uploaded on first use (held by
-// the handle); then run(env, a) with the fan's TlArgs and the receivers.
+// The prologue of every entry on a fan handle: a fan with trajectories; under its lock, once its kernel has finished (its M
+// is known then), the entry's check(M, S); the keep list and the save ranges uploaded on first use (held by the handle);
+// then run(env, a) with the fan's TlArgs (the receivers and p0 unset).
 template <typename Check, typename Run>
-static int tl_fan_entry(pgr_fan* f, const double* p0, const double* depths, int64_t R, const void* out, const char* who,
-                        Check check, Run run)
+static int fan_entry(pgr_fan* f, const char* who, Check check, Run run)
 {
     if (!f) return fail(std::string(who) + ": null fan");
     if (!f->save) return fail(std::string(who) + ": the fan was launched without trajectories (S = 0)");
     std::lock_guard<std::mutex> lock(f->m);
     HIPCHK(hipSetDevice(f->env->device));
     int rc = fan_finish(f);
-    if (!rc) rc = tl_check(f->M, f->S, p0, depths, R, out, who);
-    if (!rc) rc = check(f->S);
+    if (!rc) rc = check(f->M, f->S);
     if (rc) return rc;
     if (f->M != f->N && !f->d_keep) {
         // the columns of the surviving rays, uploaded once per fan (freed with it): dropped rays are skipped in place
@@ -317,8 +315,25 @@ static int tl_fan_entry(pgr_fan* f, const double* p0, const double* depths, int6
     a.Z = f->d.Z; a.P = f->d.P; a.T = f->d.T; a.keep = (f->M != f->N) ? f->d_keep : nullptr;
     a.N = f->N; a.M = f->M; a.S = f->S; a.blocked = f->blocked ? 1 : 0;
     a.zsign = (f->flags & PGR_STORED_SIGN) ? -1.0 : 1.0;
-    a.x = f->d.r; a.p0 = p0; a.depths = depths; a.R = R;
+    a.x = f->d.r;
     return run(f->env, a);
+}
+
+// The prologue of the tube entries on a fan handle: fan_entry with tl_check before the entry's own check(S), and the
+// receivers and p0 set.
+template <typename Check, typename Run>
+static int tl_fan_entry(pgr_fan* f, const double* p0, const double* depths, int64_t R, const void* out, const char* who,
+                        Check check, Run run)
+{
+    return fan_entry(f, who,
+                     [&](int64_t M, int32_t S) {
+                         const int rc = tl_check(M, S, p0, depths, R, out, who);
+                         return rc ? rc : check(S);
+                     },
+                     [&](const pgr_env* e, TlArgs a) {
+                         a.p0 = p0; a.depths = depths; a.R = R;
+                         return run(e, a);
+                     });
 }
 
 // The prologue of the entries on caller buffers z / p [S][N] (stored sign, every ray surviving), x [S] and with RAYS the

@@ -17,38 +17,31 @@ _NO_FE_MSG = ("Flat earth transformation has not been applied. Set `flat_earth_t
               "when creating the OceanEnvironment2D object.")
 
 
-class _FanFrame:
-    """A fan checked for the tube kernels (`who` names the caller in errors): the receiver depths, the save ranges x and the
-    source depth -- everything that can be refused without a GPU.  ``to_device`` then sets up the frame the fan was traced
-    in -- xf (mirrored for a backwards fan), the EnvHandle and its tables (cin, rin, zin), the launch slowness p0, the
-    device copies of p0 and the depths, the torch stream and the fan's device handle (None for a host fan) -- and ``run``
-    calls a tube entry there."""
+def _check_flatearth(environment, flatearth):
+    if flatearth and not hasattr(environment, "sound_speed_fe"):
+        raise ValueError(_NO_FE_MSG)
 
-    def __init__(self, rays, receiver_depths, environment, flatearth, who):
-        d = np.asarray(receiver_depths, dtype=float)
-        if d.ndim != 1 or len(d) == 0:
-            raise ValueError("receiver_depths must be a non-empty 1-D sequence")
-        if not np.all(np.isfinite(d)):
-            raise ValueError("receiver_depths must be finite")
-        if not np.all(np.diff(d) > 0):
-            raise ValueError("receiver_depths must be strictly ascending")
-        if flatearth and not hasattr(environment, "sound_speed_fe"):
-            raise ValueError(_NO_FE_MSG)
-        if len(rays) < 2:
-            raise ValueError(f"{who} needs a fan of at least 2 rays (one ray tube)")
-        sd = np.asarray(rays.source_depths, dtype=float)
-        if not np.all(sd == sd[0]):
-            raise ValueError("the fan mixes source depths: ray tubes need one source")
-        r = rays.__dict__.get("_r")
-        if r is not None and rays.__dict__.get("_rs") is None:
-            x = np.asarray(r, dtype=float)          # (a device fan: one save grid by construction)
-        else:
-            rs = np.asarray(rays.rs, dtype=float)
-            x = rs[0]
-            if not np.array_equal(rs, np.broadcast_to(x, rs.shape)):
-                raise ValueError("the rows of rays.rs differ: the fan must share one save grid")
-        self.depths, self.x, self.source_depth = np.ascontiguousarray(d), x, float(sd[0])
-        self.rays, self.environment, self.flatearth = rays, environment, flatearth
+
+def _save_grid(rays):
+    """the fan's one save grid x (S,), refused when the rows of rays.rs differ"""
+    r = rays.__dict__.get("_r")
+    if r is not None and rays.__dict__.get("_rs") is None:
+        return np.asarray(r, dtype=float)          # (a device fan: one save grid by construction)
+    rs = np.asarray(rays.rs, dtype=float)
+    x = rs[0]
+    if not np.array_equal(rs, np.broadcast_to(x, rs.shape)):
+        raise ValueError("the rows of rays.rs differ: the fan must share one save grid")
+    return x
+
+
+class _TracedFan:
+    """A fan (host or device resident) on its save ranges x, and -- after ``to_device`` -- the frame it was traced in: xf
+    (mirrored for a backwards fan), the EnvHandle and its tables (cin, rin, zin), the torch stream and the fan's device
+    handle (None for a host fan).  ``_host_fan`` uploads a host fan's arrays once.  Shared by the products that read a
+    fan's trajectories: the tube products (_FanFrame) and the travel-time kernel (sensitivity.py)."""
+
+    def __init__(self, rays, x, environment, flatearth):
+        self.rays, self.x, self.environment, self.flatearth = rays, x, environment, flatearth
 
     def to_device(self, device):
         import torch
@@ -57,12 +50,7 @@ class _FanFrame:
         self.backwards = len(x) > 1 and x[-1] < x[0]
         self.xf = -x if self.backwards else x            # the frame the fan was traced in
         self.env, self.tables = _device_env(self.environment, self.flatearth, self.backwards, device)
-        cin, rin, zin = self.tables
-        c_source = bilinear_interp(self.xf[0], self.source_depth, rin, zin, cin)
-        self.p0 = _initial_slowness(self.rays.thetas, c_source)
         self.dev = torch.device("cuda", self.env.device)
-        self.d_p0 = self.upload(self.p0)
-        self.d_depths = self.upload(self.depths)
         self.stream = torch.cuda.current_stream(self.dev).cuda_stream
         self.handle = self.rays.__dict__.get("_dev")
         if self.handle is not None and self.handle._env is not self.env:
@@ -81,6 +69,38 @@ class _FanFrame:
             a = self.xf if name == "xf" else np.asarray(getattr(self.rays, name), dtype=float).T
             self._host[name] = self.upload(a)
         return self._host[name].data_ptr()
+
+
+class _FanFrame(_TracedFan):
+    """A fan checked for the tube kernels (`who` names the caller in errors): the receiver depths, the save ranges x and the
+    source depth -- everything that can be refused without a GPU.  ``to_device`` then sets up _TracedFan's frame, the launch
+    slowness p0 and the device copies of p0 and the depths, and ``run`` calls a tube entry there."""
+
+    def __init__(self, rays, receiver_depths, environment, flatearth, who):
+        d = np.asarray(receiver_depths, dtype=float)
+        if d.ndim != 1 or len(d) == 0:
+            raise ValueError("receiver_depths must be a non-empty 1-D sequence")
+        if not np.all(np.isfinite(d)):
+            raise ValueError("receiver_depths must be finite")
+        if not np.all(np.diff(d) > 0):
+            raise ValueError("receiver_depths must be strictly ascending")
+        _check_flatearth(environment, flatearth)
+        if len(rays) < 2:
+            raise ValueError(f"{who} needs a fan of at least 2 rays (one ray tube)")
+        sd = np.asarray(rays.source_depths, dtype=float)
+        if not np.all(sd == sd[0]):
+            raise ValueError("the fan mixes source depths: ray tubes need one source")
+        super().__init__(rays, _save_grid(rays), environment, flatearth)
+        self.depths, self.source_depth = np.ascontiguousarray(d), float(sd[0])
+
+    def to_device(self, device):
+        super().to_device(device)
+        cin, rin, zin = self.tables
+        c_source = bilinear_interp(self.xf[0], self.source_depth, rin, zin, cin)
+        self.p0 = _initial_slowness(self.rays.thetas, c_source)
+        self.d_p0 = self.upload(self.p0)
+        self.d_depths = self.upload(self.depths)
+        return self
 
     def run(self, entry, *args):
         """Tube entry `entry` on the fan, with p0, the arguments after it and the stream: ``FanHandle.<entry>`` on a
