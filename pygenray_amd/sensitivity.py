@@ -15,7 +15,10 @@ from .ray_objects import EigenRays, RayFan
 from .transmission import _TracedFan, _check_flatearth, _save_grid
 
 
-def _grid(v, name):
+def _grid(v, name, most):
+    """a kernel grid axis checked; ``most`` the entry's limit (include/pgr.h), checked before the values are read"""
+    if hasattr(v, "__len__") and len(v) > most:
+        raise ValueError(f"{name} has {len(v)} values, more than the {most} supported")
     g = np.asarray(v, dtype=float)
     if g.ndim != 1 or len(g) < 2:
         raise ValueError(f"{name} must be a 1-D sequence of at least 2 values")
@@ -79,7 +82,7 @@ def travel_time_kernel(rays, environment, ranges=None, depths=None, flatearth=Tr
     on the default grid the derivative with respect to the true sound speed is ``K * F`` (F broadcast over depth).
 
     A float64 NumPy array, or with ``as_tensor=True`` the ``torch`` tensor on ``device``.  A ``ValueError`` before any GPU
-    work for a result larger than ``max_bytes``."""
+    work for a result larger than ``max_bytes``, or for more than 65535 ranges or 2^30 depths."""
     _check_flatearth(environment, flatearth)
     if isinstance(range_index, (bool, np.bool_)) or not isinstance(range_index, numbers.Integral):
         raise ValueError(f"range_index must be an integer, not {range_index!r}")
@@ -100,8 +103,8 @@ def travel_time_kernel(rays, environment, ranges=None, depths=None, flatearth=Tr
     jobs = {k: _KernelJob(f, environment, flatearth, range_index) for k, f in fans.items()}
     if ranges is None or depths is None:
         _, _, rin, zin = _unpack_envi(environment, flatearth=flatearth)[:4]
-    g = _grid(rin if ranges is None else ranges, "ranges")
-    h = _grid(zin if depths is None else depths, "depths")
+    g = _grid(rin if ranges is None else ranges, "ranges", 65535)     # (a range node is a launch's gridDim.y)
+    h = _grid(zin if depths is None else depths, "depths", 1 << 30)
     M = sum(len(f) for f in fans.values())
     size = M * len(g) * len(h) * 8
     if size > max_bytes:

@@ -1,6 +1,8 @@
 """travel_time_kernel on the GPU: the kernel alone bit for bit against the restatement (tests/ttk_reference.py) on synthetic
-fans, the default-grid identity K . cin = -(T_c - T_0), the linearisation against finite differences of re-shot fans, the
-eigenrays, one answer from every path to the same fan, and the contracted build."""
+fans and against the independent reference (tests/ttk_independent.py) within its derived rounding bound on grids of many
+tiles, the grid-size limit, the default-grid identity K . cin = -(T_c - T_0), dropped rays and the flat-earth frame, the
+linearisation against finite differences of re-shot fans, the eigenrays, one answer from every path to the same fan, and
+the contracted build."""
 import os
 import subprocess
 import sys
@@ -9,7 +11,8 @@ import numpy as np
 import pytest
 
 import ttk_reference as ttr
-from tube_gpu import SYN_R, SYN_Z, _same, _upload, munk_env, pr, pr_any, sloping_env, syn_env  # noqa: F401
+from tube_gpu import (SYN_R, SYN_Z, _same, _upload, munk_env, pr, pr_any, sloping_env,  # noqa: F401
+                      sloping_env_shallow_table, syn_env)
 
 pytestmark = pytest.mark.gpu
 
@@ -341,3 +344,123 @@ def test_contracted_identity(pr_any):
     cin, _, _ = ttr.traced_tables(env, False, False)
     _identity(K, cin, fan)
     assert _same(K, pr_any.travel_time_kernel(fan, env, flatearth=False))
+
+
+# ---- the kernel against the independent reference (tests/ttk_independent.py) --------------------------------------------
+
+def banded(B, h, S, seed):
+    """T, Z (S, M), x (S,) on the depth grid h of B nodes (tiles of 63 nodes): rays held in narrow depth bands (most tiles
+    skipped), level rays on nodes 62, 63, 125 and 126 (the tile seams), a ray weaving across the seam between cells 61
+    and 64, and rays wholly above and wholly below the grid"""
+    rng = np.random.default_rng(seed)
+    x = np.linspace(-1e3, 61e3, S)
+    rows = []
+    for b in (62, 63, 125, 126):
+        if b < B:
+            rows.append(np.full(S, h[b]))
+    if B > 65:
+        lo, hi = h[61], h[65]
+        rows.append(np.where(np.arange(S) % 2, hi, lo) + rng.uniform(-0.3, 0.3, S) * (hi - lo))   # weaving the seam
+    for c in (0.2, 0.55, 0.9):                                         # narrow bands
+        k = int(c * (B - 1))
+        rows.append(h[k] + rng.uniform(0.0, 3.0, S) * (h[min(k + 1, B - 1)] - h[k]))
+    rows.append(np.linspace(-150.0, -40.0, S))                          # above the grid
+    rows.append(np.linspace(h[-1] + 10.0, h[-1] + 300.0, S))            # below it
+    d = np.array(rows).T
+    T = np.concatenate([np.zeros((1, d.shape[1])), np.cumsum(np.hypot(np.diff(x)[:, None], np.diff(d, axis=0)), axis=0)])
+    return T / 1500.0 + rng.uniform(0.0, 1e-4, d.shape), -d, x
+
+
+@pytest.mark.parametrize("B", [126, 127, 6000])
+def test_kernel_within_the_derived_bound_of_the_independent_reference(pr, syn_env, B):
+    """B = 126 is exactly two tiles of 63 nodes, 127 two and one node, 6000 95 tiles and a partial one of 15 nodes.  The
+    tolerance is ttk_independent's bound (its docstring derives it); the restatement gives the same bits as the kernel."""
+    import ttk_independent as tti
+    env, cin = syn_env
+    g = np.array([-500.0, 7e3, 19e3, 20e3, 33e3, 47.5e3, 60e3])
+    h = np.linspace(0.0, 5000.0, B)
+    T, Z, x = banded(B, h, 24, B)
+    col = len(x) - 1
+    K = _device_kernel(env, T, Z, x, g, h, col)
+    Ki, mag, bound = tti.kernel(T, Z, x, g, h, cin, SYN_R, SYN_Z, col)
+    assert np.isfinite(K).all()
+    assert (np.abs(K - Ki) <= bound).all(), np.max(np.abs(K - Ki) - bound)
+    assert (K[bound == 0] == 0).all() and (K != 0).any()
+    assert bound.max() < 1e-9 * np.abs(Ki).max()                  # the bound is not vacuous
+    assert _same(K, ttr.kernel(T, Z, x, g, h, cin, SYN_R, SYN_Z, col))
+
+
+@pytest.mark.parametrize("S", [257, 513, 1001])
+def test_kernel_bit_identical_with_more_chords_than_lanes(pr, syn_env, S):
+    """more than 256 chords: pgr_ttk_seg and pgr_ttk_span stride a lane over several; the columns either side of 256 and 512"""
+    env, cin = syn_env
+    g = np.linspace(0.0, 60e3, 9)
+    h = _depth_grid(70)
+    T, Z, x = synthetic(9, S, S, g, h)
+    for col in sorted({c for c in (255, 256, 257, 511, 512, S - 1) if c < S}):
+        K = _device_kernel(env, T, Z, x, g, h, col)
+        assert _same(K, ttr.kernel(T, Z, x, g, h, cin, SYN_R, SYN_Z, col)), col
+
+
+def test_range_count_at_its_limits(pr, syn_env):
+    """A = 65535 (the most a launch's gridDim.y takes) for one two-sample ray: the restatement's bits.  A = 65536 through
+    the C entry: refused before any launch, the output left as it was."""
+    import torch
+    from pygenray_amd import _lib
+    env, cin = syn_env
+    x = np.array([1e3, 59e3])
+    T, Z = np.array([[0.0], [39.0]]), np.array([[-900.0], [-1400.0]])
+    h = np.array([0.0, 1000.0, 2000.0])
+    g = np.linspace(0.0, 60e3, 65535)
+    K = _device_kernel(env, T, Z, x, g, h, 1)
+    assert _same(K, ttr.kernel(T, Z, x, g, h, cin, SYN_R, SYN_Z, 1)) and (K != 0).sum() > 1000
+    g = np.linspace(0.0, 60e3, 65536)
+    t, stream = _upload(env, T, Z, x, g, h)
+    out = torch.full((1, len(g), len(h)), -1.0, dtype=torch.float64, device=t[0].device)
+    with pytest.raises(_lib.PgrError, match="n_ranges must be 2 .. 65535"):
+        _lib.travel_time_kernel_device(env, t[0].data_ptr(), t[1].data_ptr(), 1, 2, t[2].data_ptr(), t[3].data_ptr(),
+                                       len(g), t[4].data_ptr(), len(h), 1, out.data_ptr(), stream)
+    assert (out == -1.0).all()
+
+
+@pytest.mark.parametrize("blocked", [False, True], ids=["rows", "sample-blocked"])
+def test_dropped_rays(pr, blocked):
+    """a device fan whose keep list is not the identity (tables shallower than the sea floor: the deep rays leave them and
+    are dropped): one row per surviving ray, in order, the same bits as its host twin and the restatement, and the
+    default-grid identity for every row, at the last and a middle column"""
+    env = sloping_env_shallow_table(pr) if blocked else munk_env(pr, ztop=4200.0)
+    ang = np.linspace(-20, 20, 60)
+    kw = dict(flatearth=False, debug=False)
+    dev = pr.shoot_rays(1000.0, 0.0, ang, 100e3, 101, env, device_resident=True, **kw)
+    host = pr.shoot_rays(1000.0, 0.0, ang, 100e3, 101, env, device_resident=False, **kw)
+    assert 5 < len(ang) - len(dev) < 55 and len(dev) == len(host)
+    assert dev._dev._env.blocked_layout == blocked
+    g, h = np.linspace(0.0, 100e3, 17), np.linspace(0.0, 4200.0, 70)
+    cin = ttr.traced_tables(env, False, False)[0]
+    for col in (-1, 50):
+        a = pr.travel_time_kernel(dev, env, g, h, flatearth=False, range_index=col)
+        b = pr.travel_time_kernel(host, env, g, h, flatearth=False, range_index=col)
+        assert a.shape[0] == len(dev) and _same(a, b)
+        assert _same(b, ttr.fan_kernel(host, env, g, h, flatearth=False, range_index=col))
+        K = pr.travel_time_kernel(dev, env, flatearth=False, range_index=col)
+        _identity(K, cin, host, col)
+    assert dev.device_resident
+
+
+def test_flat_earth_default_environment(pr):
+    """the default environment in its flat-earth frame (non-uniform zin: the look-up's longer search): the default-grid
+    identity for every ray; device fan == host fan == restatement on a few rays of a user grid"""
+    env = pr.OceanEnvironment2D()
+    ang = np.linspace(-15, 15, 24)
+    dev = pr.shoot_rays(1000.0, 0.0, ang, 100e3, 501, env, debug=False, device_resident=True)
+    host = pr.shoot_rays(1000.0, 0.0, ang, 100e3, 501, env, debug=False, device_resident=False)
+    cin, rin, zin = ttr.traced_tables(env, True, False)
+    assert np.ptp(np.diff(zin)) > 0
+    K = pr.travel_time_kernel(dev, env)
+    assert K.shape == (len(host), len(rin), len(zin)) and np.isfinite(K).all()
+    _identity(K, cin, host)
+    assert _same(K, pr.travel_time_kernel(host, env))
+    few = pr.RayFan.from_arrays(*(np.asarray(getattr(host, n))[::8] for n in ("thetas", "rs", "ts", "zs", "ps", "n_botts",
+                                                                             "n_surfs", "source_depths")))
+    g, h = np.linspace(0.0, 100e3, 11), np.linspace(0.0, 5000.0, 40)
+    assert _same(pr.travel_time_kernel(dev, env, g, h)[::8], ttr.fan_kernel(few, env, g, h))

@@ -68,12 +68,17 @@ SYN_R = np.linspace(0.0, 60e3, 13)                           # uniform range gri
 SYN_Z = np.concatenate([np.arange(0.0, 1000.0, 20.0), np.arange(1000.0, 5001.0, 50.0)])    # non-uniform depth grid
 
 
+def syn_cin():
+    """the sound speed of syn_env's table: smooth, positive and range dependent, so that the bilinear look-up of c matters"""
+    rr, zz = np.meshgrid(SYN_R, SYN_Z, indexing="ij")
+    return 1490.0 + 0.017 * zz + 8.0 * np.sin(2 * np.pi * rr / 40e3) + 6.0 * np.exp(-((zz - 1200.0) / 500.0) ** 2)
+
+
 @pytest.fixture(scope="module")
 def syn_env(pr_any):
-    """a small range-dependent table (tables in HBM): smooth, positive, so that the bilinear look-up of c matters"""
+    """a small range-dependent table (tables in HBM): syn_cin() on SYN_R x SYN_Z"""
     from pygenray_amd import _lib
-    rr, zz = np.meshgrid(SYN_R, SYN_Z, indexing="ij")
-    cin = 1490.0 + 0.017 * zz + 8.0 * np.sin(2 * np.pi * rr / 40e3) + 6.0 * np.exp(-((zz - 1200.0) / 500.0) ** 2)
+    cin = syn_cin()
     cpin = np.gradient(cin, SYN_Z, axis=1, edge_order=1)
     nr = len(SYN_R)
     return _lib.EnvHandle(cin, cpin, SYN_R, SYN_Z, np.full(nr, 5000.0), SYN_R.copy(), np.zeros(nr)), cin
