@@ -378,13 +378,20 @@ int pgr_travel_time_kernel_device(pgr_env* env, const double* T, const double* z
  *                            a = 1 (default) the trajectories are integrated by the sample-blocked kernel
  *                            (PGR_SAMPLE_BLOCKED: full 32-byte stores, 1.2x instead of 2.3x the sample bytes written) and
  *                            un-blocked to [S][M] by the pass that squeezes dropped rays out on the way to the host;
- *                            a = 0 plain [S][N] rows.  The caller sees the same arrays, bit for bit. */
+ *                            a = 0 plain [S][N] rows.  The caller sees the same arrays, bit for bit.
+ *   PGR_OPT_D2H_REGISTER     the pipelined copy of large trajectory arrays (more than 32 MB in all) to the caller's pageable
+ *                            buffers (pgr_shoot_fan, pgr_fan_fetch_samples): a = 1 (default) helper threads page-lock each
+ *                            128 MiB sub-job (hipHostRegister) once its pages exist and the copy is one DMA into it; a = 0
+ *                            never page-lock: every sub-job is copied piece by piece through the runtime's staging, which is
+ *                            what a process under a locked-memory limit gets when the registration fails.  Same arrays,
+ *                            bit for bit (tests/test_transfer.py runs both). */
 #define PGR_OPT_WAVES_PER_BLOCK 0
 #define PGR_OPT_DEPTH_SEARCH 1
 #define PGR_OPT_PARK 2
 #define PGR_OPT_PLACEMENT 3
 #define PGR_OPT_PERSISTENT 4
 #define PGR_OPT_API_BLOCKED 5
+#define PGR_OPT_D2H_REGISTER 6
 int pgr_env_set_option(pgr_env* env, int what, int a, int b);
 
 /* Unit-level device entry points (for parity tests of a1-a8, REF/integration_processes.py):

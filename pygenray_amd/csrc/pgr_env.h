@@ -29,6 +29,10 @@ extern "C" int pgr_env_set_option(pgr_env* env, int what, int a, int b)
         if (a < 0 || a > 1) return fail("api_blocked: 0 = row layout, 1 = sample-blocked kernel for HBM-table trajectory fans of pgr_shoot_fan / pgr_fan_launch");
         env->api_blocked = a;
         return 0;
+    case PGR_OPT_D2H_REGISTER:
+        if (a < 0 || a > 1) return fail("d2h_register: 1 = page-lock the destination sub-jobs of the pipelined copy, 0 = never (piecewise staged copies, as after a failed registration)");
+        env->d2h_register = a;
+        return 0;
     case PGR_OPT_PERSISTENT:
         if (a < 0 || a > 3) return fail("persistent: 0 = static deal of whole workgroups, 1 = persistent waves + packet queue (fans of up to two rounds: waves 4 .. 7 start at the list's cheap end), 2 = every packet from the list's head, 3 = waves 4 .. 7 always start at the cheap end");
         env->persistent = a;

@@ -291,7 +291,7 @@ extern "C" int pgr_fan_fetch_samples(pgr_fan* f, double* T, double* z, double* p
             return fail("pgr_fan_fetch_samples: device allocation of the un-blocking scratch failed");
         return squeeze_rows(jb, f->blocked, squeeze ? f->keep.data() : nullptr, M, f->N, f->S, f->scratch, st);
     };
-    return d2h_pipelined(jobs, st, f->env->device, ready);
+    return d2h_pipelined(jobs, st, f->env->device, f->env->d2h_register != 0, ready);
 }
 
 #endif  // PGR_FAN_HANDLE_H

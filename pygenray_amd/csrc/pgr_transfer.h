@@ -61,14 +61,16 @@ struct OrderedPrefault {
     size_t n_pieces = 0;
     int device = 0;
 
-    OrderedPrefault(const std::vector<D2HJob>& j, int dev) : jobs(j), device(dev)
+    // `page_lock` false (PGR_OPT_D2H_REGISTER 0): every job starts as "registration failed" -- no helper registers it, the
+    // caller cannot claim it, each goes out piece by piece
+    OrderedPrefault(const std::vector<D2HJob>& j, int dev, bool page_lock) : jobs(j), device(dev)
     {
         for (auto& q : jobs) { start.push_back(total); total += q.bytes; }
         n_pieces = (total + kPiece - 1) / kPiece;
         done = std::vector<std::atomic<unsigned char>>(n_pieces);
         for (auto& d : done) d.store(0);
         reg = std::vector<std::atomic<int>>(jobs.size());
-        for (auto& r : reg) r.store(0);
+        for (auto& r : reg) r.store(page_lock ? 0 : 3);
     }
     // touch the pages of the concatenation's bytes [a, b)
     void touch(size_t a, size_t b)
@@ -141,9 +143,9 @@ struct OrderedPrefault {
 }  // namespace
 
 // `ready`: called once before the first copy (waits for the kernel and may decide, from the status array, to
-// replace the jobs' sources -- the compaction of dropped rays); returns 0 or an error
+// replace the jobs' sources -- the compaction of dropped rays); returns 0 or an error.  `page_lock`: PGR_OPT_D2H_REGISTER
 template <class Ready>
-static int d2h_pipelined(std::vector<D2HJob> jobs, hipStream_t st, int device, Ready ready)
+static int d2h_pipelined(std::vector<D2HJob> jobs, hipStream_t st, int device, bool page_lock, Ready ready)
 {
     std::vector<D2HJob> whole;
     std::vector<size_t> sub_of;
@@ -170,7 +172,7 @@ static int d2h_pipelined(std::vector<D2HJob> jobs, hipStream_t st, int device, R
         whole = jobs;
         jobs = cut;
     }
-    OrderedPrefault pf(jobs, device);
+    OrderedPrefault pf(jobs, device, page_lock);
     pf.stream = st;
     if (trace_on()) pf.t0 = t0;
     unsigned nt = std::thread::hardware_concurrency();
@@ -343,7 +345,7 @@ extern "C" int pgr_shoot_fan(pgr_env* env, const double* y0, int64_t N, double s
             return fail("pgr_shoot_fan: device allocation of the PGR_COMPACT workspace failed");
         return squeeze_rows(jb, blocked, M < N ? keep.data() : nullptr, M, N, S, env->ws2, st);
     };
-    rc = d2h_pipelined(jobs, st, env->device, ready);
+    rc = d2h_pipelined(jobs, st, env->device, env->d2h_register != 0, ready);
     if (rc) return rc;
     if (end_state) HIPCHK(hipMemcpyAsync(end_state, d.end, N * 3 * sizeof(double), hipMemcpyDeviceToHost, st));
     HIPCHK(hipMemcpyAsync(n_bott, d.nb, N * 4, hipMemcpyDeviceToHost, st));
