@@ -351,6 +351,30 @@ int pgr_travel_time_kernel_device(pgr_env* env, const double* T, const double* z
                                   const double* x, const double* ranges, int32_t n_ranges, const double* depths,
                                   int32_t n_depths, int32_t column, double* out, void* stream);
 
+/* Time fronts and turning-point counts of a fan at chosen save columns ("Time fronts and ray
+ * identifiers").  For surviving ray m (launch order) with slowness samples p_m(s), s = 0 ... S - 1, let cls(v) = +1 for
+ * v > 0, -1 for v < 0, 0 for v == +-0, a NaN being a class that differs from every class, itself included.  Then
+ *   change_m(s) = 1 if cls(p_m(s + 1)) differs from cls(p_m(s)) else 0,        s = 0 ... S - 2,
+ *   turns[c * M + m] (DEVICE int32, [n_cols][M], overwritten) = sum over s < cols[c] of change_m(s)   (0 for column 0),
+ * entry for entry np.sum(np.diff(np.sign(ps[:, :col + 1]), axis=1) != 0, axis=1): the reference's ray-identifier count
+ * (REF/ray_objects.py:142) of the path up to column col, the same in either sign convention of p.  T_out, z_out, p_out
+ * (DEVICE float64, [n_cols][M] each, overwritten) = T, z, p of the surviving rays at column cols[c], the bits the fan holds.
+ * Any of the four outputs may be NULL, not all.  cols[n_cols] (HOST, int32, each 0 .. S - 1, repeats and any order allowed,
+ * 1 <= n_cols <= 65535): slot c is column cols[c].  An integer prefix sum: no atomics, and the same answer in any order;
+ * p is read up to max(cols) only (each sample once, plus one seam sample per segment of at most 32).
+ *
+ * pgr_fan_time_front: a device-resident fan (either trajectory layout it holds; dropped rays are skipped in place, nothing
+ *   is copied or fetched).  Waits for the fan's kernel, then enqueues on `stream` and returns without synchronising.  Needs
+ *   M >= 1 and a fan launched with trajectories.
+ * pgr_time_front_device: caller buffers T, z, p (DEVICE) [n_samples][n_rays] rows on `device`, every ray kept
+ *   (M = n_rays); an input may be NULL when its output is NULL, p is needed for turns as well.  Enqueued on `stream`,
+ *   returns without synchronising. */
+int pgr_fan_time_front(pgr_fan* fan, const int32_t* cols, int32_t n_cols, double* T_out, double* z_out, double* p_out,
+                       int32_t* turns, void* stream);
+int pgr_time_front_device(int device, const double* T, const double* z, const double* p, int64_t n_rays,
+                          int32_t n_samples, const int32_t* cols, int32_t n_cols, double* T_out, double* z_out,
+                          double* p_out, int32_t* turns, void* stream);
+
 /* Tuning options of ONE environment (per-ray results never depend on them; there is no process-wide
  * state: host threads that drive different GPUs hold different environments).
  *   PGR_OPT_WAVES_PER_BLOCK  a = waves (of 64 rays) per workgroup, 0 = automatic

@@ -8,7 +8,7 @@ needs ``libpgr_hip.so`` and a GPU.
 """
 from .xr_lite import DataArray
 from .environment import OceanEnvironment2D, munk_ssp, eflat, eflatinv, flat_earth_c
-from .ray_objects import Ray, RayFan, EigenRays
+from .ray_objects import Ray, RayFan, TimeFront, EigenRays
 from .launch_rays import shoot_rays, shoot_ray, _unpack_envi
 from .eigenrays import find_eigenrays
 from .transmission import transmission_loss, beam_transmission_loss
@@ -22,7 +22,7 @@ from . import _lib
 # allowed, ~10 % faster, no bit-parity claim) -- see pygenray_amd/_lib.py
 ARITHMETIC = _lib.ARITH
 
-__all__ = ["OceanEnvironment2D", "munk_ssp", "eflat", "eflatinv", "flat_earth_c", "DataArray", "Ray", "RayFan",
+__all__ = ["OceanEnvironment2D", "munk_ssp", "eflat", "eflatinv", "flat_earth_c", "DataArray", "Ray", "RayFan", "TimeFront",
            "EigenRays", "shoot_rays", "shoot_ray", "find_eigenrays", "transmission_loss", "beam_transmission_loss", "arrivals", "Arrivals",
            "travel_time_kernel", "derivsrd", "bottom_bounce",
            "surface_bounce", "ray_bounding_box_event", "ray_angle", "bilinear_interp",

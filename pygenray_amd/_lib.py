@@ -250,7 +250,10 @@ def load():
             ("pgr_arrivals_device", [_vp, _vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _i64, _vp, i32, _vp, _i64] + [_vp] * 6),
             # the travel-time sensitivity kernel (csrc/pgr_sens.h): a per-ray product, same pair of entries
             ("pgr_fan_travel_time_kernel", [_vp, _vp, i32, _vp, i32, i32, _vp, _vp]),
-            ("pgr_travel_time_kernel_device", [_vp, _vp, _vp, _i64, i32, _vp, _vp, i32, _vp, i32, i32, _vp, _vp])):
+            ("pgr_travel_time_kernel_device", [_vp, _vp, _vp, _i64, i32, _vp, _vp, i32, _vp, i32, i32, _vp, _vp]),
+            # time fronts and turning-point counts (csrc/pgr_front.h)
+            ("pgr_fan_time_front", [_vp, _vp, i32, _vp, _vp, _vp, _vp, _vp]),
+            ("pgr_time_front_device", [ctypes.c_int, _vp, _vp, _vp, _i64, i32, _vp, i32, _vp, _vp, _vp, _vp, _vp])):
         getattr(L, name).restype = ctypes.c_int
         getattr(L, name).argtypes = argtypes
     _lib = L
@@ -569,6 +572,14 @@ class FanHandle:
         check(load().pgr_fan_travel_time_kernel(self._h, _vp(ranges_ptr), int(n_ranges), _vp(depths_ptr), int(n_depths),
                                                 int(column), _vp(out_ptr), _vp(stream or None)))
 
+    def time_front(self, cols, t_ptr, z_ptr, p_ptr, turns_ptr, stream=0):
+        """pgr_fan_time_front on raw device pointers (ints; 0 / None: not wanted): t / z / p [len(cols)][M] float64 = the
+        surviving rays' samples at the save columns `cols` (a host sequence of column indices), turns [len(cols)][M] int32
+        = their turning-point counts up to those columns (include/pgr.h).  Enqueued on `stream`."""
+        c = None if cols is None else np.ascontiguousarray(cols, dtype=np.int32)
+        check(load().pgr_fan_time_front(self._h, _vptr(c), 0 if c is None else len(c), _vp(t_ptr or None), _vp(z_ptr or None),
+                                        _vp(p_ptr or None), _vp(turns_ptr or None), _vp(stream or None)))
+
     def close(self):
         if getattr(self, "_h", None):
             load().pgr_fan_destroy(self._h)
@@ -702,3 +713,15 @@ def travel_time_kernel_device(env, t_ptr, z_ptr, n_rays, n_samples, x_ptr, range
     check(load().pgr_travel_time_kernel_device(env._h, _vp(t_ptr), _vp(z_ptr), int(n_rays), int(n_samples), _vp(x_ptr),
                                                _vp(ranges_ptr), int(n_ranges), _vp(depths_ptr), int(n_depths), int(column),
                                                _vp(out_ptr), _vp(stream or None)))
+
+
+def time_front_device(device, t_ptr, z_ptr, p_ptr, n_rays, n_samples, cols, t_out_ptr, z_out_ptr, p_out_ptr, turns_ptr,
+                      stream=0):
+    """pgr_time_front_device on raw device pointers (ints; 0 / None: absent): the samples at the save columns `cols` (a
+    host sequence, or None for a NULL list) and the turning-point counts up to them, of caller buffers T / z / p
+    [n_samples][n_rays] on `device`; see include/pgr.h."""
+    c = None if cols is None else np.ascontiguousarray(cols, dtype=np.int32)
+    check(load().pgr_time_front_device(int(device), _vp(t_ptr or None), _vp(z_ptr or None), _vp(p_ptr or None), int(n_rays),
+                                       int(n_samples), _vptr(c), 0 if c is None else len(c), _vp(t_out_ptr or None),
+                                       _vp(z_out_ptr or None), _vp(p_out_ptr or None), _vp(turns_ptr or None),
+                                       _vp(stream or None)))

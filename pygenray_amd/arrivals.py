@@ -6,23 +6,8 @@ already are -- in HBM for a device-resident fan, uploaded through torch for a ho
 """
 import numpy as np
 
+from .ray_objects import _columns
 from .transmission import _FanFrame
-
-
-def _columns(range_indices, S):
-    """range_indices -> int32 column indices in 0 .. S - 1 (negative ones counted from the end)."""
-    if range_indices is None:
-        return np.array([S - 1], dtype=np.int32)
-    ri = np.atleast_1d(np.asarray(range_indices))
-    if ri.ndim != 1 or len(ri) == 0:
-        raise ValueError("range_indices must be a non-empty 1-D sequence of column indices")
-    if ri.dtype.kind not in "iu":
-        raise ValueError("range_indices must be integers")
-    if not np.all((ri >= -S) & (ri < S)):
-        raise ValueError(f"range_indices must lie in -{S} .. {S - 1} (the fan has {S} save ranges)")
-    if len(ri) > 65535:
-        raise ValueError("at most 65535 range_indices")
-    return np.ascontiguousarray(np.where(ri < 0, ri + S, ri), dtype=np.int32)
 
 
 def _bilinear(x, y, x_grid, y_grid, values):
@@ -52,10 +37,18 @@ class Arrivals:
       ``received_angle`` = degrees(arcsin(p c(x, D_j))) with c from the tables of the frame the fan was traced in
       (``host_physics.ray_angle``'s definition; ``EigenRays.received_angles`` uses the non-flat-earth table instead).
 
+    - ``turning_points`` (n_arrivals, 2) int64: the turning points of rays ``tube`` and ``tube + 1`` on their way to the
+      arrival's column (``RayFan.turning_points``); ``ray_number`` (float): the count the two share times the sign of
+      ``launch_angle`` -- the reference's numeric ray id, what tomography matches arrivals to predictions by -- and NaN
+      where the two edge rays differ: a tube straddling a turning point has no one identifier.  Both are ``None`` for an
+      ``Arrivals`` built without the counts.
+
     Bounce counts are known only at a ray's end: at the fan's last column, ``rays.n_surfs[tube]`` and
     ``rays.n_botts[tube]`` apply.  The source's own column (r = 0) has no arrivals."""
 
-    def __init__(self, offsets, receiver_depths, ranges, range_indices, tube, w, time, p, intensity, thetas, c_rx):
+    def __init__(self, offsets, receiver_depths, ranges, range_indices, tube, w, time, p, intensity, thetas, c_rx,
+                 turning_points=None):
+        self.turning_points = turning_points
         self.offsets = offsets
         self.receiver_depths = receiver_depths
         self.ranges = ranges
@@ -101,6 +94,15 @@ class Arrivals:
                 self._lazy["received_angle"] = np.degrees(np.arcsin(self.p * self._c_rx[j, c]))
         return self._lazy["received_angle"]
 
+    @property
+    def ray_number(self):
+        if self.turning_points is None:
+            return None
+        if "ray_number" not in self._lazy:
+            a, b = self.turning_points[:, 0], self.turning_points[:, 1]
+            self._lazy["ray_number"] = np.where(a == b, a * np.sign(self.launch_angle), np.nan)
+        return self._lazy["ray_number"]
+
     def at(self, j, c):
         """The arrivals at receiver j and requested column slot c -> dict of arrays (views)."""
         n = len(self.range_indices)
@@ -145,9 +147,14 @@ def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=N
     cin, rin, zin = f.tables
     xs = f.xf[cols]
     c_rx = _bilinear(np.broadcast_to(xs[None, :], (R, n)), np.broadcast_to(f.depths[:, None], (R, n)), rin, zin, cin)
-    return Arrivals(offsets.cpu().numpy(), f.depths, np.asarray(f.x)[cols], cols.astype(np.int64), tube.cpu().numpy(),
+    offsets, tube = offsets.cpu().numpy(), tube.cpu().numpy()
+    # the edge rays' turning points at each arrival's column: one more call on the fan where it is (NumPy on a host fan)
+    turns = rays.turning_points(cols)
+    slot = np.repeat(np.arange(R * n), np.diff(offsets)) % n
+    turns = np.stack([turns[tube, slot], turns[tube + 1, slot]], axis=1)
+    return Arrivals(offsets, f.depths, np.asarray(f.x)[cols], cols.astype(np.int64), tube,
                     w.cpu().numpy(), T.cpu().numpy(), P.cpu().numpy(), I.cpu().numpy(), np.asarray(rays.thetas, dtype=float),
-                    c_rx)
+                    c_rx, turns)
 
 
 __all__ = ["arrivals", "Arrivals"]

@@ -56,3 +56,4 @@
 #include "pgr_arrivals.h"       // ray-tube arrivals at receiver depths: pgr_fan_arrival_counts, pgr_fan_arrivals, ..._device
 #include "pgr_beams.h"          // Gaussian-beam intensity: pgr_fan_beam_intensity, pgr_beam_intensity_device
 #include "pgr_sens.h"           // travel-time sensitivity kernels: pgr_fan_travel_time_kernel, pgr_travel_time_kernel_device
+#include "pgr_front.h"          // time fronts and turning-point counts: pgr_fan_time_front, pgr_time_front_device

@@ -9,6 +9,29 @@ without materialising per-ray Python objects.
 import numpy as np
 
 
+def _columns(range_indices, S):
+    """range_indices -> int32 column indices in 0 .. S - 1 (negative ones counted from the end)."""
+    if range_indices is None:
+        return np.array([S - 1], dtype=np.int32)
+    ri = np.atleast_1d(np.asarray(range_indices))
+    if ri.ndim != 1 or len(ri) == 0:
+        raise ValueError("range_indices must be a non-empty 1-D sequence of column indices")
+    if ri.dtype.kind not in "iu":
+        raise ValueError("range_indices must be integers")
+    if not np.all((ri >= -S) & (ri < S)):
+        raise ValueError(f"range_indices must lie in -{S} .. {S - 1} (the fan has {S} save ranges)")
+    if len(ri) > 65535:
+        raise ValueError("at most 65535 range_indices")
+    return np.ascontiguousarray(np.where(ri < 0, ri + S, ri), dtype=np.int32)
+
+
+def _id_strings(numbers, n_botts, n_surfs):
+    """the reference's ray-id strings (REF/ray_objects.py:143-155): the numeric id as text, 'b' when the ray touched a
+    boundary"""
+    txt = numbers.astype(str)  # same text as str(np.float64): '-3.0', '0.0', ...
+    return np.where((n_botts == 0) & (n_surfs == 0), txt, np.char.add(txt, "b"))
+
+
 class Ray:
     """Single ray (REF/ray_objects.py:7-59).  ``y`` is ODE-convention [T; z; p] of shape (3, S)."""
 
@@ -187,10 +210,69 @@ class RayFan:
         if len(self.thetas) == 0:
             self.ray_ids = np.array([], dtype=str)
             return
-        ray_ids = np.sum(np.diff(np.sign(self.ps)) != 0, axis=1) * (np.sign(self.thetas))
-        b_mask = (self.n_botts == 0) & (self.n_surfs == 0)
-        txt = ray_ids.astype(str)  # same text as str(np.float64): '-3.0', '0.0', ...
-        self.ray_ids = np.where(b_mask, txt, np.char.add(txt, "b"))
+        if self._ps_in_hbm():      # the count from the kernel, where the fan is: no (M, S) block crosses PCIe for M integers
+            turns = self.turning_points()[:, 0]
+        else:
+            turns = np.sum(np.diff(np.sign(self.ps)) != 0, axis=1)
+        self.ray_ids = _id_strings(turns * np.sign(self.thetas), self.n_botts, self.n_surfs)
+
+    # ---- turning points and time fronts at any save column ----
+    def _ps_in_hbm(self):
+        """a device-resident fan whose ps has not been fetched"""
+        return self.__dict__.get("_dev") is not None and "_ps" not in self.__dict__
+
+    def _n_save(self):
+        dev = self.__dict__.get("_dev")
+        return dev.S if dev is not None else np.shape(self.ps)[1]
+
+    def _front_device(self, cols, samples):
+        """pgr_fan_time_front on the fan in HBM -> turns (M, n) int64 and, with `samples`, t, z, p (M, n); nothing else is
+        fetched and the fan stays device resident"""
+        import torch
+        h = self._dev
+        dev = torch.device("cuda", h._env.device)
+        n, M = len(cols), len(self.thetas)
+        turns = torch.empty((n, M), dtype=torch.int32, device=dev)
+        tzp = [torch.empty((n, M), dtype=torch.float64, device=dev) for _ in range(3 if samples else 0)]
+        h.time_front(cols, *([a.data_ptr() for a in tzp] or [0, 0, 0]), turns.data_ptr(),
+                     torch.cuda.current_stream(dev).cuda_stream)
+        return (turns.cpu().numpy().T.astype(np.int64),) + tuple(a.cpu().numpy().T for a in tzp)
+
+    def turning_points(self, range_indices=None):
+        """The number of turning points of every ray on its way to the save columns ``range_indices`` (default ``[S - 1]``,
+        the receiver range; any integers in -S .. S - 1) -> ``(M, n)`` int64: the sign changes of p up to each column,
+        ``np.sum(np.diff(np.sign(ps[:, :col + 1]), axis=1) != 0, axis=1)`` -- the reference's ray-id count
+        (REF/ray_objects.py:142) applied to the path so far.  A device-resident fan whose ``ps`` has not been read is
+        counted where it is (csrc/pgr_front.h) and stays device resident; the values are the same either way."""
+        cols = _columns(range_indices, self._n_save())
+        if len(self.thetas) == 0:
+            return np.zeros((0, len(cols)), dtype=np.int64)
+        if self._ps_in_hbm():
+            return self._front_device(cols, False)[0]
+        ps = np.asarray(self.ps)
+        if len(cols) == 1:
+            return np.sum(np.diff(np.sign(ps[:, :cols[0] + 1]), axis=1) != 0, axis=1).astype(np.int64)[:, None]
+        last = int(cols.max())
+        run = np.zeros((ps.shape[0], last + 1), dtype=np.int64)         # run[:, c]: the changes in front of column c
+        np.cumsum(np.diff(np.sign(ps[:, :last + 1]), axis=1) != 0, axis=1, out=run[:, 1:])
+        return run[:, cols]
+
+    def time_front(self, range_idx=-1):
+        """The time front at save column ``range_idx`` (an integer in -S .. S - 1) -> ``TimeFront``: travel time, depth,
+        slowness and turning-point count of every ray there.  A device-resident fan hands over that one column of each
+        array (csrc/pgr_front.h) and stays device resident; ``ts[:, k]``, ``zs[:, k]``, ``ps[:, k]`` bit for bit."""
+        if np.ndim(range_idx) != 0:
+            raise ValueError("range_idx must be one column index")
+        S = self._n_save()
+        k = int(_columns(range_idx, S)[0])
+        M = len(self.thetas)
+        if self.device_resident and M:
+            turns, t, z, p = (a[:, 0] for a in self._front_device([k], True))
+        else:
+            turns = self.turning_points([k])[:, 0]
+            t, z, p = (np.asarray(a)[:, k] for a in (self.ts, self.zs, self.ps))
+        rng = np.asarray(self.rs)[:, k] if M else np.zeros(0)
+        return TimeFront(rng, k, self.thetas, t, z, p, turns, self.ray_ids if k == S - 1 else None)
 
     def __len__(self):
         return len(self.thetas)
@@ -250,23 +332,8 @@ class RayFan:
     # ---- plots (REF/ray_objects.py:157-260) ----
     def plot_time_front(self, include_lines=False, range_idx=-1, add_colorbar=True, ray_id=False,
                         **kwargs):
-        from matplotlib import pyplot as plt
-        if include_lines:
-            plt.plot(self.ts[:, range_idx], self.zs[:, range_idx], c="#aaaaaa", lw=0.5, zorder=5)
-        kw = {"c": self.thetas, "cmap": "viridis", "s": 2, "lw": 0, "zorder": 6}
-        kw.update(kwargs)
-        if ray_id:
-            cats = np.unique(self.ray_ids)
-            colors = plt.cm.tab20(np.linspace(0, 1, len(cats)))
-            lut = dict(zip(cats, colors))
-            kw.update({"c": [lut[c] for c in self.ray_ids]})
-            kw.pop("cmap", None)
-            add_colorbar = False
-        plt.scatter(self.ts[:, range_idx], self.zs[:, range_idx], **kw)
-        if add_colorbar:
-            plt.colorbar(label="launch angle [°]")
-        plt.xlabel("time [s]")
-        plt.ylabel("depth [m]")
+        self.time_front(range_idx).plot(include_lines=include_lines, add_colorbar=add_colorbar,
+                                        ray_id=self.ray_ids if ray_id else False, **kwargs)
 
     def plot_ray_fan(self, **kwargs):
         from matplotlib import pyplot as plt
@@ -284,6 +351,61 @@ class RayFan:
         plt.scatter(self.thetas, self.zs[:, -1], **kw)
         plt.xlabel("launch angle [°]")
         plt.ylabel("depth [m]")
+
+
+class TimeFront:
+    """The time front of a fan at one save column (``RayFan.time_front``; what the reference's ``plot_time_front(range_idx=k)``
+    scatters, REF/ray_objects.py:157-222), host arrays over the fan's M rays:
+
+    - ``range`` (M,): the column's range; ``range_index``: the column k (0 .. S - 1)
+    - ``thetas``: launch angles, degrees, ``RayFan.thetas``
+    - ``t``, ``z``, ``p``: ``ts[:, k]``, ``zs[:, k]``, ``ps[:, k]``, the stored sign convention, bit for bit
+    - ``turning_points`` (int64): the sign changes of p on the way to column k (``RayFan.turning_points``)
+    - ``ray_numbers``: ``turning_points * np.sign(thetas)``, the reference's numeric ray id (REF/ray_objects.py:142)
+    - ``ray_ids``: the reference's strings, the number with a ``b`` suffix for a ray that touched a boundary.  The bounce
+      counts ``n_botts`` / ``n_surfs`` are known only at a ray's end, so the strings exist at the fan's last column (where
+      they equal ``RayFan.ray_ids``) and are ``None`` at every other column."""
+
+    def __init__(self, range, range_index, thetas, t, z, p, turning_points, ray_ids=None):   # noqa: A002
+        self.range = range
+        self.range_index = range_index
+        self.thetas = thetas
+        self.t, self.z, self.p = t, z, p
+        self.turning_points = turning_points
+        self.ray_ids = ray_ids
+
+    def __len__(self):
+        return len(self.thetas)
+
+    @property
+    def ray_numbers(self):
+        return self.turning_points * np.sign(self.thetas)
+
+    def plot(self, include_lines=False, add_colorbar=True, ray_id=False, **kwargs):
+        """The scatter of ``RayFan.plot_time_front``: depth against travel time, coloured by launch angle, or with
+        ``ray_id`` by ray id: True for this front's own (``ray_ids``, else ``ray_numbers``), or one label per ray."""
+        from matplotlib import pyplot as plt
+        if include_lines:
+            plt.plot(self.t, self.z, c="#aaaaaa", lw=0.5, zorder=5)
+        kw = {"c": self.thetas, "cmap": "viridis", "s": 2, "lw": 0, "zorder": 6}
+        kw.update(kwargs)
+        if ray_id is not False and ray_id is not None:
+            ids = ray_id if not isinstance(ray_id, (bool, np.bool_)) else (
+                self.ray_ids if self.ray_ids is not None else self.ray_numbers.astype(str))
+            cats = np.unique(ids)
+            colors = plt.cm.tab20(np.linspace(0, 1, len(cats)))
+            lut = dict(zip(cats, colors))
+            kw.update({"c": [lut[c] for c in ids]})
+            kw.pop("cmap", None)
+            add_colorbar = False
+        plt.scatter(self.t, self.z, **kw)
+        if add_colorbar:
+            plt.colorbar(label="launch angle [°]")
+        plt.xlabel("time [s]")
+        plt.ylabel("depth [m]")
+
+    def __repr__(self):
+        return f"TimeFront({len(self)} rays at column {self.range_index})"
 
 
 class EigenRays:
@@ -384,4 +506,4 @@ class EigenRays:
         io.savemat(filename, {"eigenrays": data})
 
 
-__all__ = ["Ray", "RayFan", "EigenRays"]
+__all__ = ["Ray", "RayFan", "TimeFront", "EigenRays"]
