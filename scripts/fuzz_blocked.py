@@ -1,5 +1,7 @@
 """PGR_SAMPLE_BLOCKED against the row layout over the random environments of tests/helpers.random_case that take the HBM-table
-path (range-dependent sound speed): every ray, every sample, NaN columns, padding rows pre-filled.  usage: python scripts/fuzz_blocked.py [first:last]   (default 20000:20600)"""
+path (range-dependent sound speed): every ray, every sample, NaN columns, padding rows pre-filled.  The GPU suite carries a slice of this sweep, checked against
+the oracle as well: tests/test_hip_parity.py::test_save_paths_on_random_environments_are_bit_identical_to_the_oracle (SAVE 0 / 1 / 3
+through DeviceFan, a fan handle fetched with and without compaction).  usage: python scripts/fuzz_blocked.py [first:last]   (default 20000:20600)"""
 import sys, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT); sys.path.insert(0, os.path.join(ROOT, "tests"))

@@ -1,7 +1,9 @@
 """Persistent waves over the random environments of tests/helpers.random_case (every depth-search form, LDS- and HBM-table
 kernels, rows and the sample-blocked layout, loose and tight tolerances, mirrored frames): a fan of 135 000 ... 300 000 rays
 of each environment under PGR_OPT_PERSISTENT 0 / 1 / 2 / 3 -- every output array of every ray the same bits -- and every
-400th ray of the default mode against the oracle (oracle.MATH_CR) bit for bit.
+400th ray of the default mode against the oracle (oracle.MATH_CR) bit for bit.  The GPU suite carries a slice of this sweep
+(three random environments, the default mode, every 400th ray against the oracle) at the end of
+tests/test_hip_parity.py::test_save_paths_on_random_environments_are_bit_identical_to_the_oracle.
 usage (GPU box): python scripts/fuzz_persistent.py [first:last] [flatearth]"""
 import sys, os, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

@@ -1965,3 +1965,114 @@ def test_random_environments_are_bit_identical_to_the_oracle(lib):
         st = assert_bit_parity(g, o, label=f"seed {seed}{' (flat earth)' if flat else ''}: {desc}")
         n_rays += st["n"]; n_odd += st["odd"]
     assert n_rays > 6000 and n_odd == 0 and n_cubic >= 8, (n_rays, n_odd, n_cubic)
+
+
+def _end_states_equal_the_oracle(t, o, label):
+    """rule (A) without samples: status, bounce counts, accepted and rejected steps and end states of the rays in `t`"""
+    assert np.array_equal(t["status"], o["status"]), label
+    ok = o["status"] == 0
+    end_o = np.stack([o["T"][:, -1], o["z"][:, -1], o["p"][:, -1]], 1)
+    for name, a_, b_ in (("end", t["end"], end_o), ("n_bott", t["n_bott"], o["n_bott"]), ("n_surf", t["n_surf"], o["n_surf"]),
+                         ("n_steps", t["n_steps"].astype(np.int64), o["n_steps"]), ("n_rej", t["n_rej"].astype(np.int64), o["n_rej"])):
+        assert np.array_equal(a_[ok], b_[ok]), (label, name)
+    return int(ok.sum())
+
+
+def test_save_paths_on_random_environments_are_bit_identical_to_the_oracle(lib):
+    """The slice of scripts/fuzz_blocked.py and scripts/fuzz_persistent.py the suite carries: the random environments of
+    helpers.random_case, seeds 600 ... 635 as they are and 700 ... 711 through the flat-earth map (disjoint from
+    test_random_environments_are_bit_identical_to_the_oracle, which launches SAVE 2 through the host-pointer entry only),
+    on the save paths API callers get.  Each environment is launched through DeviceFan end-state-only (SAVE 0), on the
+    default sample path (SAVE 1, rows) and -- on the HBM-table path -- sample-blocked (SAVE 3), and through a FanHandle
+    fetched with and without the compaction of dropped rays; pgr_debug_last_instance confirms the SAVE value that ran, and
+    EVERY launch is checked against the oracle (MATH_CR) by rule (A), samples=False for SAVE 1 / 3.  Then three fans large
+    enough for persistent waves (> 8 x 256 x 64 rays, short range), every 400th ray against the oracle."""
+    import torch
+    from pygenray_amd.device_fan import DeviceFan
+    from pygenray_amd.environment import eflat
+    PER_RAY = ("end", "n_bott", "n_surf", "status", "n_steps", "n_rej")
+
+    def device_fan(env, y0, kw, S, save, blocked, want_save, label, persist=None):
+        fan = DeviceFan(env, y0, kw["x0"], kw["x1"], S, rtol=kw["rtol"], terminate_backwards=kw["terminate_backwards"],
+                        save=save, sample_major=True, sample_blocked=blocked)
+        if save:
+            for t in (fan.T, fan.Z, fan.P):
+                t.fill_(123.0)                      # nothing of a surviving ray is left unwritten
+        fan.run(); torch.cuda.synchronize()
+        li = env.last_instance()
+        assert li["save"] == want_save, (label, li)
+        assert persist is None or li["persist"] == persist, (label, li)
+        out = {k: getattr(fan, k).cpu().numpy() for k in PER_RAY}
+        if save:
+            out.update({k: fan.rows(getattr(fan, k.upper())).cpu().numpy().T.copy() for k in "Tzp"})
+        return out
+
+    def flat_mapped(arrs):
+        cin, cpin, rin, zin, depths, dr, ba = arrs
+        zf = eflat(zin, 35.0)[0]
+        cf = np.array([eflat(zin, 35.0, row)[1] for row in cin])
+        return [cf, np.gradient(cf, zf, axis=1, edge_order=1), rin, zf, eflat(depths, 35.0)[0], dr, ba]
+
+    n = dict(envs=0, hbm=0, blocked=0, dropped=0, rays=0, launches=0)
+    for seed, flat in [(k, False) for k in range(600, 636)] + [(k, True) for k in range(700, 712)]:
+        arrs, (src, x0, th), kw, desc = random_case(seed, n_rays=96)
+        if flat:
+            arrs = flat_mapped(arrs)
+        label = f"seed {seed}{' (flat earth)' if flat else ''}: {desc}"
+        y0 = y0_for(oracle, arrs, src, x0, th)
+        S = kw["S"]
+        o = oracle.shoot_fan(*arrs, y0, kw["x0"], kw["x1"], S, rtol=kw["rtol"], math=oracle.MATH_CR,
+                             terminate_backwards=kw["terminate_backwards"])
+        env = lib.EnvHandle(*arrs)
+        n["rays"] += _end_states_equal_the_oracle(device_fan(env, y0, kw, S, False, False, 0, label + ", SAVE 0"), o,
+                                                  label + ", SAVE 0")
+        assert_bit_parity(device_fan(env, y0, kw, S, True, False, 1, label + ", SAVE 1"), o, label=label + ", SAVE 1",
+                          samples=False)
+        n["launches"] += 2
+        if not env.lds_path:
+            n["hbm"] += 1
+            if env.blocked_layout:
+                assert_bit_parity(device_fan(env, y0, kw, S, True, True, 3, label + ", SAVE 3"), o, label=label + ", SAVE 3",
+                                  samples=False)
+                n["blocked"] += 1
+                n["launches"] += 1
+        # a fan handle (results in HBM: sample-blocked where the environment takes it), fetched both ways
+        h = lib.FanHandle(env, kw["x0"], kw["x1"], S, y0=y0, rtol=kw["rtol"], terminate_backwards=kw["terminate_backwards"])
+        N, M = h.wait()
+        assert env.last_instance()["save"] == (3 if env.blocked_layout else 1), label
+        ok = o["status"] == 0
+        assert (N, M) == (len(y0), int(ok.sum())), label
+        g = h.fetch_rays()
+        full = h.fetch_samples(compact=False)
+        assert_bit_parity(dict(g, **{k: full[k].T for k in "Tzp"}), o, label=label + ", fan handle", samples=False)
+        squeezed = h.fetch_samples(compact=True)
+        for k in "Tzp":
+            assert squeezed[k].shape == (S, M) and np.array_equal(squeezed[k], full[k][:, ok]), (label, k)
+        h.close()
+        n["launches"] += 1
+        n["dropped"] += bool(M < N)
+        n["envs"] += 1
+        env.close()
+    assert n["hbm"] >= 12 and n["blocked"] >= 12 and n["envs"] - n["hbm"] >= 12 and n["dropped"] >= 4 and n["rays"] > 4000, n
+    # fans of several rounds of persistent waves: every 400th ray against the oracle
+    checked = 0
+    for seed, save, blocked in ((650, False, False), (651, True, False), (653, True, True)):    # HBM, LDS, HBM tables
+        arrs, (src, x0, th), kw, desc = random_case(seed)
+        env = lib.EnvHandle(*arrs)
+        assert not (blocked and not env.blocked_layout), desc
+        n_big = 8 * 256 * 64 + 4097 + 1000 * (seed - 650)
+        kw = dict(kw, x1=kw["x0"] + min(kw["x1"] - kw["x0"], 8e3))
+        S = 5
+        y0 = y0_for(oracle, arrs, src, x0, np.linspace(th[0], th[-1], n_big))
+        label = f"seed {seed}, {n_big} rays: {desc}"
+        out = device_fan(env, y0, kw, S, save, blocked, 3 if blocked else int(save), label, persist=1)
+        sub = np.arange(0, n_big, 400)
+        o = oracle.shoot_fan(*arrs, y0[sub], kw["x0"], kw["x1"], S, rtol=kw["rtol"], math=oracle.MATH_CR,
+                             terminate_backwards=kw["terminate_backwards"])
+        t = {k: v[sub] for k, v in out.items()}
+        checked += _end_states_equal_the_oracle(t, o, label)
+        if save:
+            assert_bit_parity(t, o, label=label, samples=False)
+        env.close()
+    assert checked > 1000, checked
+    print(f"\nsave paths on random environments: {n}; {checked} rays of three persistent fans against the oracle")

@@ -113,6 +113,65 @@ def test_mirror_arrays():
     np.testing.assert_array_equal(out[5], [-3.0, 2, -1])
 
 
+def test_independent_frame_tables_equal_the_unpacked_ones_bit_for_bit(golden_dir):
+    """tests/frame_independent.py (the frame derivation the random-environment product tests check transmission.py
+    against) on the golden tables of test_unpack_matches_reference_tables: its own read of the DataArrays and its own
+    flat-earth map give _unpack_envi's arrays to the bit (and the reference's, as closely as _unpack_envi does); its mirror,
+    bottom interpolation and launch slowness give the pinned host helpers' bits on a backwards frame with the bathymetry
+    on a range grid of its own."""
+    import frame_independent as fi
+    from pygenray_amd.host_physics import bilinear_interp, linear_interp
+    from pygenray_amd.launch_rays import _initial_slowness
+    z = np.linspace(0.0, 6000.0, 400)
+    r = np.linspace(0.0, 50e3, 30)
+    env = OceanEnvironment2D(DataArray(np.outer(np.ones(30), munk_ssp(z)), dims=["range", "depth"],
+                                       coords={"range": r, "depth": z}),
+                             DataArray(np.full(30, 5000.0), dims=["range"], coords={"range": r}),
+                             flat_earth_transform=False)
+    g = np.load(os.path.join(golden_dir, "g1_fixture_case.npz"))
+    keys = ["cin", "rin", "zin", "depths", "depth_ranges"]
+    pick = lambda seven: [seven[0], seven[2], seven[3], seven[4], seven[5]]   # noqa: E731
+    for a, b, k in zip(fi.tables(env, False), pick(_unpack_envi(env, flatearth=False)), keys):
+        assert a.dtype == np.float64 and np.array_equal(a, b), k
+        np.testing.assert_array_equal(a, g["env_" + k])
+    g = np.load(os.path.join(golden_dir, "g5_flatearth.npz"))
+    zf = np.arange(0, 6000, 4.0)
+    rf = np.linspace(0.0, 100e3, 100)
+    env = OceanEnvironment2D(DataArray(np.outer(np.ones(100), munk_ssp(zf)), dims=["range", "depth"],
+                                       coords={"range": rf, "depth": zf}),
+                             DataArray(np.linspace(4500, 4900, 100), dims=["range"], coords={"range": rf}),
+                             lat=35.0, flat_earth_transform=True)
+    for a, b, k in zip(fi.tables(env, True), pick(_unpack_envi(env, flatearth=True)), keys):
+        assert np.array_equal(a, b), k
+        np.testing.assert_allclose(a, g["env_" + k], rtol=1e-15, atol=0)
+    assert not np.array_equal(fi.tables(env, True)[2], fi.tables(env, False)[2])
+    # range-dependent, depth-major, another latitude, the bathymetry on its own (non-uniform) range grid: forwards and
+    # backwards, flat earth on and off
+    rng = np.random.default_rng(7)
+    rr = np.sort(np.concatenate([[-30e3, 90e3], rng.uniform(-30e3, 90e3, 15)]))
+    br = np.sort(np.concatenate([[-30e3, 90e3], rng.uniform(-30e3, 90e3, 7)]))
+    c = np.array([munk_ssp(zf, 1100.0 + 3e-3 * ri) for ri in rr])
+    env = OceanEnvironment2D(DataArray(c.T, dims=["depth", "range"], coords={"range": rr, "depth": zf}),
+                             DataArray(4600.0 + 200 * np.sin(br / 17e3), dims=["range"], coords={"range": br}), lat=-52.5)
+    for fe in (False, True):
+        seven = _unpack_envi(env, flatearth=fe)
+        for a, b, k in zip(fi.tables(env, fe), pick(seven), keys):
+            assert np.array_equal(a, b), (fe, k)
+        x = np.linspace(70e3, -10e3, 23)
+        xf, cin, rin, zin, bd, bdr = fi.traced_frame(env, x, fe)
+        m = _mirror_envi_arrays(seven[0], seven[1], seven[2], seven[4], seven[5], seven[6])
+        assert np.array_equal(xf, -x) and xf[0] == -70e3
+        for a, b in zip((cin, rin, zin, bd, bdr), (m[0], m[2], seven[3], m[3], m[4])):
+            assert np.array_equal(a, b)
+        assert np.array_equal(fi.bottom_at(xf, bd, bdr), [linear_interp(float(v), m[4], m[3]) for v in xf])
+        assert not np.array_equal(fi.bottom_at(xf, bd, bdr), fi.bottom_at(xf, seven[4], seven[5]))
+        th = np.linspace(-17, 21, 90)
+        assert np.array_equal(fi.launch_slowness(th, 830.0, xf, cin, rin, zin),
+                              _initial_slowness(th, bilinear_interp(xf[0], 830.0, m[2], seven[3], m[0])))
+        fwd = fi.traced_frame(env, x[::-1], fe)
+        assert np.array_equal(fwd[0], x[::-1]) and np.array_equal(fwd[1], seven[0]) and np.array_equal(fwd[5], seven[5])
+
+
 # ---------------------------------------------------------------- containers (REF tests/test_ray_objects.py)
 def _make_rays(M=3, N=10, R=10000.0):
     rays = []
