@@ -375,6 +375,69 @@ int pgr_time_front_device(int device, const double* T, const double* z, const do
                           int32_t n_samples, const int32_t* cols, int32_t n_cols, double* T_out, double* z_out,
                           double* p_out, int32_t* turns, void* stream);
 
+/* Running path integral of every ray of a fan at every save range ("Path integrals and volume
+ * absorption").  For surviving ray m (launch order) with samples s = 0 ... S - 1: depth d_s (= -z in the stored convention),
+ * travel time T_s, save range x_s in the frame the fan was traced in, c_s the bilinear sound speed of pgr_fan_intensity at
+ * (x_s, d_s), and alpha_s = alpha(d_s) from the profile alpha[n_a] (dB per metre, finite, >= 0) at the strictly ascending
+ * depth nodes a_depths[n_a] (metres, positive down, the frame's depths):
+ *   n_a == 1: alpha_s = alpha[0] (a_depths may be NULL);
+ *   else alpha[0] for d_s <= a_depths[0], alpha[n_a - 1] for d_s >= a_depths[n_a - 1], and in between, with the cell
+ *   j = np.searchsorted(a_depths, d_s, side="right") - 1 clamped to 0 ... n_a - 2,
+ *   alpha_j + w (alpha_j+1 - alpha_j),  w = (d_s - a_depths_j) / (a_depths_j+1 - a_depths_j);  NaN for a NaN depth.
+ * Then, with q_s = alpha_s c_s,
+ *   inc_s = (0.5 (q_s + q_s+1)) (T_s+1 - T_s)   [dB],   s = 0 ... S - 2   (the trapezoid rule on ds = c dT),
+ *   out[0 * M + m] = 0.0,   out[(s + 1) * M + m] = out[s * M + m] + inc_s   sequentially, in increasing s.
+ * out (DEVICE, float64 [S][M], rows over the SURVIVING rays whatever the fan's own layout; every entry is written).  A NaN in
+ * T or d propagates by IEEE rules: the ray's entries are NaN from that sample on (entry 0 is 0.0 regardless).  The division
+ * is correctly rounded and nothing is contracted (reference build).  alpha == {1.0}: the path length in metres -- in the
+ * traced frame: for a flat-earth environment the flat-earth length, which exceeds the true one by a factor of at most
+ * exp(z / R_earth), about 1 + 8e-4 at 5 km.  No atomics: one lane forms each ray's sums in the order above, so repeated calls
+ * are bit-equal and equal the sequential sum.
+ *
+ * a_depths, alpha are HOST arrays, checked before any device work (n_a < 1, nodes that are not finite or do not ascend, an
+ * alpha that is not finite or negative and NULL pointers are errors, and nothing is written).
+ * pgr_fan_path_integral: a device-resident fan (either trajectory layout it holds; dropped rays are skipped in place, nothing
+ *   is copied or fetched).  Waits for the fan's kernel, then enqueues on `stream` and returns without synchronising.  Needs
+ *   M >= 1 and a fan launched with trajectories.
+ * pgr_path_integral_device: caller buffers T, z (DEVICE) [n_samples][n_rays] rows, stored sign convention, every ray kept
+ *   (M = n_rays), x[n_samples] (DEVICE) the save ranges in the frame of `env`. */
+int pgr_fan_path_integral(pgr_fan* fan, const double* a_depths, const double* alpha, int32_t n_a, double* out, void* stream);
+int pgr_path_integral_device(pgr_env* env, const double* T, const double* z, int64_t n_rays, int32_t n_samples,
+                             const double* x, const double* a_depths, const double* alpha, int32_t n_a, double* out,
+                             void* stream);
+
+/* The weights volume absorption gives the tube products: W[i] = 10^(-A[i] / 10) for a path integral A in dB (DEVICE, n
+ * entries each; W may be A itself), computed as exp(y), y = -(A[i] K), K = 0x1.d791c5f888822p-3 the double nearest
+ * ln(10) / 10, with the library's own exp of pgr_fan_beam_intensity (a fixed sequence of + - x, rint and ldexp; within
+ * 1.5 ulp on [-700, 0]); 0.0 for y < -700 and NaN for a NaN.  Enqueued on `stream`, returns without synchronising. */
+int pgr_absorption_weights_device(int device, const double* A, int64_t n, double* W, void* stream);
+
+/* Weighted twins of the tube entries: the same calls with `weights` (DEVICE, float64 [S][M] rows over the surviving rays,
+ * as pgr_fan_path_integral writes them; [n_samples][n_rays] for the _device entries), after which every g of the
+ * definitions above is g W[s * M + m] -- so I_k = 0.5 (g_k W_k + g_k+1 W_k+1) |dp0| / (r |dz|), the beams' E_k likewise, and
+ * an arrival's I is the weighted tube's.  Validity tests and the intervals [lo, hi) are those of the unweighted calls, so
+ * the tubes counted, their order and pgr_fan_arrival_counts / pgr_arrival_counts_device are unchanged by finite weights
+ * (there is no weighted count); a NaN weight makes its sample one that adds nothing, as a NaN sample does.  weights == NULL:
+ * exactly the unweighted entry, which is this call with NULL (the same bits). */
+int pgr_fan_intensity_w(pgr_fan* fan, const double* p0, const double* weights, const double* depths, int64_t n_depths,
+                        double* out, void* stream);
+int pgr_intensity_device_w(pgr_env* env, const double* z, const double* p, int64_t n_rays, int32_t n_samples,
+                           const double* x, const double* p0, const double* weights, const double* depths,
+                           int64_t n_depths, double* out, void* stream);
+int pgr_fan_beam_intensity_w(pgr_fan* fan, const double* p0, const double* weights, const double* bottom,
+                             const double* depths, int64_t n_depths, double min_width, double* out, void* stream);
+int pgr_beam_intensity_device_w(pgr_env* env, const double* z, const double* p, int64_t n_rays, int32_t n_samples,
+                                const double* x, const double* p0, const double* weights, const double* bottom,
+                                const double* depths, int64_t n_depths, double min_width, double* out, void* stream);
+int pgr_fan_arrivals_w(pgr_fan* fan, const double* p0, const double* weights, const double* depths, int64_t n_depths,
+                       const int32_t* cols, int32_t n_cols, const int64_t* offsets, int64_t n_arrivals, int32_t* tube,
+                       double* w, double* T, double* p, double* I, void* stream);
+int pgr_arrivals_device_w(pgr_env* env, const double* T, const double* z, const double* p, int64_t n_rays,
+                          int32_t n_samples, const double* x, const double* p0, const double* weights,
+                          const double* depths, int64_t n_depths, const int32_t* cols, int32_t n_cols,
+                          const int64_t* offsets, int64_t n_arrivals, int32_t* tube, double* w, double* T_out,
+                          double* p_out, double* I, void* stream);
+
 /* Tuning options of ONE environment (per-ray results never depend on them; there is no process-wide
  * state: host threads that drive different GPUs hold different environments).
  *   PGR_OPT_WAVES_PER_BLOCK  a = waves (of 64 rays) per workgroup, 0 = automatic

@@ -14,6 +14,7 @@ from .eigenrays import find_eigenrays
 from .transmission import transmission_loss, beam_transmission_loss
 from .arrivals import arrivals, Arrivals
 from .sensitivity import travel_time_kernel
+from .absorption import thorp_absorption, path_length, path_loss
 from .host_physics import (derivsrd, bottom_bounce, surface_bounce, ray_bounding_box_event,
                            ray_angle, bilinear_interp, linear_interp, vertical_ray)
 from . import _lib
@@ -24,6 +25,6 @@ ARITHMETIC = _lib.ARITH
 
 __all__ = ["OceanEnvironment2D", "munk_ssp", "eflat", "eflatinv", "flat_earth_c", "DataArray", "Ray", "RayFan", "TimeFront",
            "EigenRays", "shoot_rays", "shoot_ray", "find_eigenrays", "transmission_loss", "beam_transmission_loss", "arrivals", "Arrivals",
-           "travel_time_kernel", "derivsrd", "bottom_bounce",
+           "travel_time_kernel", "thorp_absorption", "path_length", "path_loss", "derivsrd", "bottom_bounce",
            "surface_bounce", "ray_bounding_box_event", "ray_angle", "bilinear_interp",
            "linear_interp", "vertical_ray"]

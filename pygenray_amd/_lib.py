@@ -253,7 +253,17 @@ def load():
             ("pgr_travel_time_kernel_device", [_vp, _vp, _vp, _i64, i32, _vp, _vp, i32, _vp, i32, i32, _vp, _vp]),
             # time fronts and turning-point counts (csrc/pgr_front.h)
             ("pgr_fan_time_front", [_vp, _vp, i32, _vp, _vp, _vp, _vp, _vp]),
-            ("pgr_time_front_device", [ctypes.c_int, _vp, _vp, _vp, _i64, i32, _vp, i32, _vp, _vp, _vp, _vp, _vp])):
+            ("pgr_time_front_device", [ctypes.c_int, _vp, _vp, _vp, _i64, i32, _vp, i32, _vp, _vp, _vp, _vp, _vp]),
+            # path integrals and absorption weights (csrc/pgr_path.h), then the weighted twins of the tube entries
+            ("pgr_fan_path_integral", [_vp, _vp, _vp, i32, _vp, _vp]),
+            ("pgr_path_integral_device", [_vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, i32, _vp, _vp]),
+            ("pgr_absorption_weights_device", [ctypes.c_int, _vp, _i64, _vp, _vp]),
+            ("pgr_fan_intensity_w", [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+            ("pgr_fan_beam_intensity_w", [_vp, _vp, _vp, _vp, _vp, _i64, f64, _vp, _vp]),
+            ("pgr_fan_arrivals_w", [_vp, _vp, _vp, _vp, _i64, _vp, i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+            ("pgr_intensity_device_w", [_vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
+            ("pgr_beam_intensity_device_w", [_vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _vp, _vp, _i64, f64, _vp, _vp]),
+            ("pgr_arrivals_device_w", [_vp, _vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _vp, _i64, _vp, i32, _vp, _i64] + [_vp] * 6)):
         getattr(L, name).restype = ctypes.c_int
         getattr(L, name).argtypes = argtypes
     _lib = L
@@ -538,15 +548,32 @@ class FanHandle:
         return {k: (v.reshape(-1)[:self.S * cols].reshape(self.S, cols) if cols != self.N else v)
                 for k, v in bufs.items() if v is not None}
 
-    def intensity(self, p0_ptr, depths_ptr, n_depths, out_ptr, stream=0):
+    def intensity(self, p0_ptr, depths_ptr, n_depths, out_ptr, stream=0, weights=0):
         """pgr_fan_intensity on raw device pointers (ints): out[n_depths][S] = the ray-tube intensity of this fan's surviving
-        rays at the receiver depths (include/pgr.h); p0 holds the M surviving rays' launch slowness.  Enqueued on `stream`."""
+        rays at the receiver depths (include/pgr.h); p0 holds the M surviving rays' launch slowness.  Enqueued on `stream`.
+        `weights` (here and in beam_intensity / arrivals): a device pointer to [S][M] weights of g, which selects the entry's
+        weighted twin (pgr_fan_intensity_w); 0: the unweighted entry."""
+        if weights:
+            return check(load().pgr_fan_intensity_w(self._h, _vp(p0_ptr), _vp(weights), _vp(depths_ptr), int(n_depths),
+                                                    _vp(out_ptr), _vp(stream or None)))
         check(load().pgr_fan_intensity(self._h, _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vp(out_ptr),
                                        _vp(stream or None)))
 
-    def beam_intensity(self, p0_ptr, bottom_ptr, depths_ptr, n_depths, min_width, out_ptr, stream=0):
+    def path_integral(self, a_depths, alpha, out_ptr, stream=0):
+        """pgr_fan_path_integral: out[S][M] (device pointer) = the running path integral of this fan's surviving rays for
+        the absorption profile alpha (dB/m) on the depth nodes a_depths (host sequences; a_depths None with one alpha)."""
+        al = _c(alpha).reshape(-1)
+        ad = None if a_depths is None else _c(a_depths).reshape(-1)
+        if ad is not None and len(ad) != len(al):
+            raise ValueError("a_depths and alpha must have equal length")
+        check(load().pgr_fan_path_integral(self._h, _vptr(ad), _vptr(al), len(al), _vp(out_ptr), _vp(stream or None)))
+
+    def beam_intensity(self, p0_ptr, bottom_ptr, depths_ptr, n_depths, min_width, out_ptr, stream=0, weights=0):
         """pgr_fan_beam_intensity on raw device pointers (ints): out[n_depths][S] = the Gaussian-beam intensity of this fan's
         surviving rays at the receiver depths, bottom[S] the bottom depth at each save range (include/pgr.h)."""
+        if weights:
+            return check(load().pgr_fan_beam_intensity_w(self._h, _vp(p0_ptr), _vp(weights), _vp(bottom_ptr), _vp(depths_ptr),
+                                                         int(n_depths), float(min_width), _vp(out_ptr), _vp(stream or None)))
         check(load().pgr_fan_beam_intensity(self._h, _vp(p0_ptr), _vp(bottom_ptr), _vp(depths_ptr), int(n_depths),
                                             float(min_width), _vp(out_ptr), _vp(stream or None)))
 
@@ -558,10 +585,14 @@ class FanHandle:
                                             _vp(counts_ptr), _vp(stream or None)))
 
     def arrivals(self, p0_ptr, depths_ptr, n_depths, cols, offsets_ptr, n_arrivals, tube_ptr, w_ptr, t_ptr, p_ptr, i_ptr,
-                 stream=0):
+                 stream=0, weights=0):
         """pgr_fan_arrivals: the arrivals themselves, written from offsets[j * len(cols) + c] into tube (int32) / w / T / p /
         I (device pointers holding n_arrivals each)."""
         c = np.ascontiguousarray(cols, dtype=np.int32)
+        if weights:
+            return check(load().pgr_fan_arrivals_w(self._h, _vp(p0_ptr), _vp(weights), _vp(depths_ptr), int(n_depths),
+                                                   _vptr(c), len(c), _vp(offsets_ptr), int(n_arrivals), _vp(tube_ptr),
+                                                   _vp(w_ptr), _vp(t_ptr), _vp(p_ptr), _vp(i_ptr), _vp(stream or None)))
         check(load().pgr_fan_arrivals(self._h, _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vptr(c), len(c),
                                       _vp(offsets_ptr), int(n_arrivals), _vp(tube_ptr), _vp(w_ptr), _vp(t_ptr), _vp(p_ptr),
                                       _vp(i_ptr), _vp(stream or None)))
@@ -669,17 +700,29 @@ def arrival_histogram_device(device, t_ptr, t_stride, status_ptr, status_stride,
                                          _vp(counts_ptr), _vp(stream or None)))
 
 
-def intensity_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, depths_ptr, n_depths, out_ptr, stream=0):
+def intensity_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, depths_ptr, n_depths, out_ptr, stream=0,
+                     weights=0):
     """pgr_intensity_device on raw device pointers (ints): the ray-tube intensity of caller buffers z / p [n_samples][n_rays]
-    (stored sign convention) on `env` (an EnvHandle); see include/pgr.h."""
+    (stored sign convention) on `env` (an EnvHandle); see include/pgr.h.  `weights` (here and in beam_intensity_device /
+    arrivals_device): a device pointer to [n_samples][n_rays] weights of g, which selects the entry's weighted twin
+    (pgr_intensity_device_w); 0: the unweighted entry."""
+    if weights:
+        return check(load().pgr_intensity_device_w(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples), _vp(x_ptr),
+                                                   _vp(p0_ptr), _vp(weights), _vp(depths_ptr), int(n_depths), _vp(out_ptr),
+                                                   _vp(stream or None)))
     check(load().pgr_intensity_device(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples), _vp(x_ptr),
                                       _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vp(out_ptr), _vp(stream or None)))
 
 
 def beam_intensity_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, bottom_ptr, depths_ptr, n_depths, min_width,
-                          out_ptr, stream=0):
+                          out_ptr, stream=0, weights=0):
     """pgr_beam_intensity_device on raw device pointers (ints): the Gaussian-beam intensity of caller buffers z / p
     [n_samples][n_rays] (stored sign convention) on `env` (an EnvHandle); see include/pgr.h."""
+    if weights:
+        return check(load().pgr_beam_intensity_device_w(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples),
+                                                        _vp(x_ptr), _vp(p0_ptr), _vp(weights), _vp(bottom_ptr),
+                                                        _vp(depths_ptr), int(n_depths), float(min_width), _vp(out_ptr),
+                                                        _vp(stream or None)))
     check(load().pgr_beam_intensity_device(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples), _vp(x_ptr),
                                            _vp(p0_ptr), _vp(bottom_ptr), _vp(depths_ptr), int(n_depths), float(min_width),
                                            _vp(out_ptr), _vp(stream or None)))
@@ -696,10 +739,16 @@ def arrival_counts_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, d
 
 
 def arrivals_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, depths_ptr, n_depths, cols, offsets_ptr,
-                    n_arrivals, tube_ptr, w_ptr, t_out_ptr, p_out_ptr, i_ptr, stream=0):
+                    n_arrivals, tube_ptr, w_ptr, t_out_ptr, p_out_ptr, i_ptr, stream=0, weights=0):
     """pgr_arrivals_device on raw device pointers (ints): arrival_counts_device's walk, writing the arrivals; see
     include/pgr.h."""
     c = np.ascontiguousarray(cols, dtype=np.int32)
+    if weights:
+        return check(load().pgr_arrivals_device_w(env._h, _vp(t_ptr), _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples),
+                                                  _vp(x_ptr), _vp(p0_ptr), _vp(weights), _vp(depths_ptr), int(n_depths),
+                                                  _vptr(c), len(c), _vp(offsets_ptr), int(n_arrivals), _vp(tube_ptr),
+                                                  _vp(w_ptr), _vp(t_out_ptr), _vp(p_out_ptr), _vp(i_ptr),
+                                                  _vp(stream or None)))
     check(load().pgr_arrivals_device(env._h, _vp(t_ptr), _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples),
                                      _vp(x_ptr), _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vptr(c), len(c),
                                      _vp(offsets_ptr), int(n_arrivals), _vp(tube_ptr), _vp(w_ptr), _vp(t_out_ptr),
@@ -725,3 +774,21 @@ def time_front_device(device, t_ptr, z_ptr, p_ptr, n_rays, n_samples, cols, t_ou
                                        int(n_samples), _vptr(c), 0 if c is None else len(c), _vp(t_out_ptr or None),
                                        _vp(z_out_ptr or None), _vp(p_out_ptr or None), _vp(turns_ptr or None),
                                        _vp(stream or None)))
+
+
+def path_integral_device(env, t_ptr, z_ptr, n_rays, n_samples, x_ptr, a_depths, alpha, out_ptr, stream=0):
+    """pgr_path_integral_device on raw device pointers (ints): out[n_samples][n_rays] = the running path integral of caller
+    buffers T / z [n_samples][n_rays] (stored sign convention) on `env` (an EnvHandle) for the absorption profile alpha
+    (dB/m) on the depth nodes a_depths (host sequences; a_depths None with one alpha); see include/pgr.h."""
+    al = _c(alpha).reshape(-1)
+    ad = None if a_depths is None else _c(a_depths).reshape(-1)
+    if ad is not None and len(ad) != len(al):
+        raise ValueError("a_depths and alpha must have equal length")
+    check(load().pgr_path_integral_device(env._h, _vp(t_ptr), _vp(z_ptr), int(n_rays), int(n_samples), _vp(x_ptr), _vptr(ad),
+                                          _vptr(al), len(al), _vp(out_ptr), _vp(stream or None)))
+
+
+def absorption_weights_device(device, a_ptr, n, w_ptr, stream=0):
+    """pgr_absorption_weights_device on raw device pointers (ints): W[i] = 10^(-A[i] / 10) for n path integrals in dB (W may
+    be A); see include/pgr.h."""
+    check(load().pgr_absorption_weights_device(int(device), _vp(a_ptr), int(n), _vp(w_ptr), _vp(stream or None)))

@@ -7,7 +7,7 @@ already are -- in HBM for a device-resident fan, uploaded through torch for a ho
 import numpy as np
 
 from .ray_objects import _columns
-from .transmission import _FanFrame
+from .transmission import _FanFrame, _absorption_profile
 
 
 def _bilinear(x, y, x_grid, y_grid, values):
@@ -118,7 +118,7 @@ class Arrivals:
                 f"{len(self.range_indices)} ranges)")
 
 
-def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=None, device=0):
+def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=None, device=0, absorption=None):
     """Ray-tube arrivals of ``rays`` (a ``RayFan`` from ``shoot_rays``) at ``receiver_depths`` (metres, positive down,
     strictly ascending) and the save columns ``range_indices`` (default ``[S - 1]``, the receiver range; any integers in
     -S .. S - 1) -> ``Arrivals``.
@@ -126,11 +126,17 @@ def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=N
     Every tube that ``transmission_loss`` counts at a receiver is one arrival: travel time and slowness interpolated
     linearly in depth across the tube, the tube's intensity, its index into the fan.  The arguments, the frame (flat-earth,
     mirrored for a backwards fan) and the sound speed are ``transmission_loss``'s.  A device-resident fan is processed
-    where it is and stays device resident."""
+    where it is and stays device resident.
+
+    ``absorption``: volume absorption as in ``transmission_loss`` -- ``intensity`` (and ``amplitude``, its square root) is
+    the weighted tube's term, which still adds up to the weighted ``transmission_loss`` bit for bit; the arrivals found,
+    their order, times and slownesses do not change.  None (default) runs exactly the call without it; the weights take
+    one trajectory array of device memory for the duration of the call."""
+    profile = None if absorption is None else _absorption_profile(absorption)
     f = _FanFrame(rays, receiver_depths, environment, flatearth, "arrivals")
     S = len(f.x)
     cols = _columns(range_indices, S)
-    f.to_device(device)
+    f.to_device(device).absorb(profile)
     import torch
 
     R, n = len(f.depths), len(cols)

@@ -92,19 +92,49 @@ extern "C" int pgr_fan_arrival_counts(pgr_fan* f, const double* p0, const double
                                       const int32_t* cols, int32_t n_cols, int64_t* counts, void* stream)
 {
     const char* who = "pgr_fan_arrival_counts";
-    return tl_fan_entry(f, p0, depths, n_depths, counts, who, [&](int32_t S) { return arr_check(cols, n_cols, S, who); },
+    return tl_fan_entry(f, p0, nullptr, depths, n_depths, counts, who, [&](int32_t S) { return arr_check(cols, n_cols, S, who); },
                         [&](const pgr_env* e, const TlArgs& a) { return arr_run(e, a, cols, n_cols, {counts}, stream, who); });
+}
+
+// the emit entries and their weighted twins (`who`: the entry named in errors)
+static int arr_fan_emit(pgr_fan* f, const double* p0, const double* W, const double* depths, int64_t n_depths,
+                        const int32_t* cols, int32_t n_cols, const int64_t* offsets, int64_t n_arrivals, int32_t* tube,
+                        double* w, double* T, double* p, double* I, void* stream, const char* who)
+{
+    const ArrOut o{nullptr, offsets, n_arrivals, tube, w, T, p, I};
+    return tl_fan_entry(f, p0, W, depths, n_depths, offsets, who,
+                        [&](int32_t S) { return arr_check_emit(cols, n_cols, S, offsets, n_arrivals, tube, w, T, p, I, who); },
+                        [&](const pgr_env* e, const TlArgs& a) { return arr_run(e, a, cols, n_cols, o, stream, who); });
+}
+
+static int arr_buffer_emit(pgr_env* env, const double* T, const double* z, const double* p, int64_t n_rays,
+                           int32_t n_samples, const double* x, const double* p0, const double* W, const double* depths,
+                           int64_t n_depths, const int32_t* cols, int32_t n_cols, const int64_t* offsets,
+                           int64_t n_arrivals, int32_t* tube, double* w, double* T_out, double* p_out, double* I,
+                           void* stream, const char* who)
+{
+    const ArrOut o{nullptr, offsets, n_arrivals, tube, w, T_out, p_out, I};
+    return tl_buffer_entry<true>(env, T, z, p, n_rays, n_samples, x, p0, W, depths, n_depths, offsets, who,
+                                 [&](int32_t S) {
+                                     return arr_check_emit(cols, n_cols, S, offsets, n_arrivals, tube, w, T_out, p_out, I, who);
+                                 },
+                                 [&](const pgr_env* e, const TlArgs& a) { return arr_run(e, a, cols, n_cols, o, stream, who); });
 }
 
 extern "C" int pgr_fan_arrivals(pgr_fan* f, const double* p0, const double* depths, int64_t n_depths, const int32_t* cols,
                                 int32_t n_cols, const int64_t* offsets, int64_t n_arrivals, int32_t* tube, double* w,
                                 double* T, double* p, double* I, void* stream)
 {
-    const char* who = "pgr_fan_arrivals";
-    const ArrOut o{nullptr, offsets, n_arrivals, tube, w, T, p, I};
-    return tl_fan_entry(f, p0, depths, n_depths, offsets, who,
-                        [&](int32_t S) { return arr_check_emit(cols, n_cols, S, offsets, n_arrivals, tube, w, T, p, I, who); },
-                        [&](const pgr_env* e, const TlArgs& a) { return arr_run(e, a, cols, n_cols, o, stream, who); });
+    return arr_fan_emit(f, p0, nullptr, depths, n_depths, cols, n_cols, offsets, n_arrivals, tube, w, T, p, I, stream,
+                        "pgr_fan_arrivals");
+}
+
+extern "C" int pgr_fan_arrivals_w(pgr_fan* f, const double* p0, const double* weights, const double* depths,
+                                  int64_t n_depths, const int32_t* cols, int32_t n_cols, const int64_t* offsets,
+                                  int64_t n_arrivals, int32_t* tube, double* w, double* T, double* p, double* I, void* stream)
+{
+    return arr_fan_emit(f, p0, weights, depths, n_depths, cols, n_cols, offsets, n_arrivals, tube, w, T, p, I, stream,
+                        "pgr_fan_arrivals_w");
 }
 
 extern "C" int pgr_arrival_counts_device(pgr_env* env, const double* z, const double* p, int64_t n_rays, int32_t n_samples,
@@ -112,7 +142,7 @@ extern "C" int pgr_arrival_counts_device(pgr_env* env, const double* z, const do
                                          const int32_t* cols, int32_t n_cols, int64_t* counts, void* stream)
 {
     const char* who = "pgr_arrival_counts_device";
-    return tl_buffer_entry<false>(env, nullptr, z, p, n_rays, n_samples, x, p0, depths, n_depths, counts, who,
+    return tl_buffer_entry<false>(env, nullptr, z, p, n_rays, n_samples, x, p0, nullptr, depths, n_depths, counts, who,
                                   [&](int32_t S) { return arr_check(cols, n_cols, S, who); },
                                   [&](const pgr_env* e, const TlArgs& a) {
                                       return arr_run(e, a, cols, n_cols, {counts}, stream, who);
@@ -125,13 +155,18 @@ extern "C" int pgr_arrivals_device(pgr_env* env, const double* T, const double* 
                                    int64_t n_arrivals, int32_t* tube, double* w, double* T_out, double* p_out, double* I,
                                    void* stream)
 {
-    const char* who = "pgr_arrivals_device";
-    const ArrOut o{nullptr, offsets, n_arrivals, tube, w, T_out, p_out, I};
-    return tl_buffer_entry<true>(env, T, z, p, n_rays, n_samples, x, p0, depths, n_depths, offsets, who,
-                                 [&](int32_t S) {
-                                     return arr_check_emit(cols, n_cols, S, offsets, n_arrivals, tube, w, T_out, p_out, I, who);
-                                 },
-                                 [&](const pgr_env* e, const TlArgs& a) { return arr_run(e, a, cols, n_cols, o, stream, who); });
+    return arr_buffer_emit(env, T, z, p, n_rays, n_samples, x, p0, nullptr, depths, n_depths, cols, n_cols, offsets,
+                           n_arrivals, tube, w, T_out, p_out, I, stream, "pgr_arrivals_device");
+}
+
+extern "C" int pgr_arrivals_device_w(pgr_env* env, const double* T, const double* z, const double* p, int64_t n_rays,
+                                     int32_t n_samples, const double* x, const double* p0, const double* weights,
+                                     const double* depths, int64_t n_depths, const int32_t* cols, int32_t n_cols,
+                                     const int64_t* offsets, int64_t n_arrivals, int32_t* tube, double* w, double* T_out,
+                                     double* p_out, double* I, void* stream)
+{
+    return arr_buffer_emit(env, T, z, p, n_rays, n_samples, x, p0, weights, depths, n_depths, cols, n_cols, offsets,
+                           n_arrivals, tube, w, T_out, p_out, I, stream, "pgr_arrivals_device_w");
 }
 
 #endif  // PGR_ARRIVALS_H

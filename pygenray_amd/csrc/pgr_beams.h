@@ -174,14 +174,38 @@ static int gb_intensity(const pgr_env* env, const TlArgs& a, const double* botto
     return tube_run(env, g, GB_TUBES, pgr_gb_bounds, nullptr, 0, (hipStream_t)stream, who, pgr_gb_sum);
 }
 
-extern "C" int pgr_fan_beam_intensity(pgr_fan* f, const double* p0, const double* bottom, const double* depths,
-                                      int64_t n_depths, double min_width, double* out, void* stream)
+// the two entries and their weighted twins (`who`: the entry named in errors)
+static int gb_fan_intensity(pgr_fan* f, const double* p0, const double* W, const double* bottom, const double* depths,
+                            int64_t n_depths, double min_width, double* out, void* stream, const char* who)
 {
-    const char* who = "pgr_fan_beam_intensity";
-    return tl_fan_entry(f, p0, depths, n_depths, out, who, [&](int32_t) { return gb_check(bottom, min_width, who); },
+    return tl_fan_entry(f, p0, W, depths, n_depths, out, who, [&](int32_t) { return gb_check(bottom, min_width, who); },
                         [&](const pgr_env* e, const TlArgs& a) {
                             return gb_intensity(e, a, bottom, min_width, out, stream, who);
                         });
+}
+
+static int gb_buffer_intensity(pgr_env* env, const double* z, const double* p, int64_t n_rays, int32_t n_samples,
+                               const double* x, const double* p0, const double* W, const double* bottom,
+                               const double* depths, int64_t n_depths, double min_width, double* out, void* stream,
+                               const char* who)
+{
+    return tl_buffer_entry<false>(env, nullptr, z, p, n_rays, n_samples, x, p0, W, depths, n_depths, out, who,
+                                  [&](int32_t) { return gb_check(bottom, min_width, who); },
+                                  [&](const pgr_env* e, const TlArgs& a) {
+                                      return gb_intensity(e, a, bottom, min_width, out, stream, who);
+                                  });
+}
+
+extern "C" int pgr_fan_beam_intensity(pgr_fan* f, const double* p0, const double* bottom, const double* depths,
+                                      int64_t n_depths, double min_width, double* out, void* stream)
+{
+    return gb_fan_intensity(f, p0, nullptr, bottom, depths, n_depths, min_width, out, stream, "pgr_fan_beam_intensity");
+}
+
+extern "C" int pgr_fan_beam_intensity_w(pgr_fan* f, const double* p0, const double* weights, const double* bottom,
+                                        const double* depths, int64_t n_depths, double min_width, double* out, void* stream)
+{
+    return gb_fan_intensity(f, p0, weights, bottom, depths, n_depths, min_width, out, stream, "pgr_fan_beam_intensity_w");
 }
 
 extern "C" int pgr_beam_intensity_device(pgr_env* env, const double* z, const double* p, int64_t n_rays,
@@ -189,12 +213,17 @@ extern "C" int pgr_beam_intensity_device(pgr_env* env, const double* z, const do
                                          const double* depths, int64_t n_depths, double min_width, double* out,
                                          void* stream)
 {
-    const char* who = "pgr_beam_intensity_device";
-    return tl_buffer_entry<false>(env, nullptr, z, p, n_rays, n_samples, x, p0, depths, n_depths, out, who,
-                                  [&](int32_t) { return gb_check(bottom, min_width, who); },
-                                  [&](const pgr_env* e, const TlArgs& a) {
-                                      return gb_intensity(e, a, bottom, min_width, out, stream, who);
-                                  });
+    return gb_buffer_intensity(env, z, p, n_rays, n_samples, x, p0, nullptr, bottom, depths, n_depths, min_width, out,
+                               stream, "pgr_beam_intensity_device");
+}
+
+extern "C" int pgr_beam_intensity_device_w(pgr_env* env, const double* z, const double* p, int64_t n_rays,
+                                           int32_t n_samples, const double* x, const double* p0, const double* weights,
+                                           const double* bottom, const double* depths, int64_t n_depths, double min_width,
+                                           double* out, void* stream)
+{
+    return gb_buffer_intensity(env, z, p, n_rays, n_samples, x, p0, weights, bottom, depths, n_depths, min_width, out,
+                               stream, "pgr_beam_intensity_device_w");
 }
 
 #endif  // PGR_BEAMS_H

@@ -57,3 +57,4 @@
 #include "pgr_beams.h"          // Gaussian-beam intensity: pgr_fan_beam_intensity, pgr_beam_intensity_device
 #include "pgr_sens.h"           // travel-time sensitivity kernels: pgr_fan_travel_time_kernel, pgr_travel_time_kernel_device
 #include "pgr_front.h"          // time fronts and turning-point counts: pgr_fan_time_front, pgr_time_front_device
+#include "pgr_path.h"           // path integrals, absorption weights: pgr_fan_path_integral, pgr_path_integral_device

@@ -42,6 +42,7 @@ struct TlArgs {
     int32_t ncol;             // slots (S when cols is NULL)
     double* bounds;           // [ncol][nchunk][2]
     double* out;              // [R][S]
+    const double* W;          // weights of g, [S][M] rows over the surviving rays (pgr_path.h); NULL: none
 };
 
 // where surviving ray m's sample s lies in Z / P (dropped rays skipped through the keep list)
@@ -152,7 +153,8 @@ __device__ __forceinline__ void tube_walk(const TlArgs& a, int slot, double d, i
 
 // Lane t's ray m of column s when `in`, else all NaN: its depth d, slowness p (stored sign), with RAYS its travel time T,
 // its launch slowness q0 and g = c / sqrt(1 - (p c)^2) (NaN for a NaN sample or |p c| >= 1).  Every tube shape loads its
-// rays here, so TL, the arrivals and the beams see the same bits of g.
+// rays here, so TL, the arrivals and the beams see the same bits of g.  With weights (a.W, uniform in the launch) g is
+// g W[s][m]: a NaN weight makes the sample one that adds nothing, as a NaN g does.
 struct TlRay { double d, p, T, q0, g; };
 
 template <bool RAYS>
@@ -170,6 +172,7 @@ __device__ __forceinline__ TlRay tl_ray(const TlArgs& a, const Ctx<false, 0>& C,
             C.lookup(x, y.d, cv, cp);
             const double pc = y.p * cv;
             if (fabs(pc) < 1.0) y.g = fdiv(cv, fsqrt(1.0 - pc * pc));
+            if (a.W && y.g == y.g) y.g = y.g * a.W[(int64_t)s * a.M + m];
         }
     }
     return y;
@@ -320,10 +323,10 @@ static int fan_entry(pgr_fan* f, const char* who, Check check, Run run)
 }
 
 // The prologue of the tube entries on a fan handle: fan_entry with tl_check before the entry's own check(S), and the
-// receivers and p0 set.
+// receivers, p0 and the weights W (NULL: none) set.
 template <typename Check, typename Run>
-static int tl_fan_entry(pgr_fan* f, const double* p0, const double* depths, int64_t R, const void* out, const char* who,
-                        Check check, Run run)
+static int tl_fan_entry(pgr_fan* f, const double* p0, const double* W, const double* depths, int64_t R, const void* out,
+                        const char* who, Check check, Run run)
 {
     return fan_entry(f, who,
                      [&](int64_t M, int32_t S) {
@@ -331,17 +334,18 @@ static int tl_fan_entry(pgr_fan* f, const double* p0, const double* depths, int6
                          return rc ? rc : check(S);
                      },
                      [&](const pgr_env* e, TlArgs a) {
-                         a.p0 = p0; a.depths = depths; a.R = R;
+                         a.p0 = p0; a.W = W; a.depths = depths; a.R = R;
                          return run(e, a);
                      });
 }
 
 // The prologue of the entries on caller buffers z / p [S][N] (stored sign, every ray surviving), x [S] and with RAYS the
-// travel times T: an environment, the buffers, tl_check and the entry's own check(S); then run(env, a) on env's device.
+// travel times T, the weights W [S][N] (NULL: none): an environment, the buffers, tl_check and the entry's own check(S); then
+// run(env, a) on env's device.
 template <bool RAYS, typename Check, typename Run>
 static int tl_buffer_entry(const pgr_env* env, const double* T, const double* z, const double* p, int64_t n_rays,
-                           int32_t n_samples, const double* x, const double* p0, const double* depths, int64_t R,
-                           const void* out, const char* who, Check check, Run run)
+                           int32_t n_samples, const double* x, const double* p0, const double* W, const double* depths,
+                           int64_t R, const void* out, const char* who, Check check, Run run)
 {
     if (!env) return fail(std::string(who) + ": null environment");
     if ((RAYS && !T) || !z || !p || !x) return fail(std::string(who) + ": null argument");
@@ -353,7 +357,7 @@ static int tl_buffer_entry(const pgr_env* env, const double* T, const double* z,
     a.Z = z; a.P = p; a.T = T; a.keep = nullptr;
     a.N = n_rays; a.M = n_rays; a.S = n_samples; a.blocked = 0;
     a.zsign = -1.0;
-    a.x = x; a.p0 = p0; a.depths = depths; a.R = R;
+    a.x = x; a.p0 = p0; a.W = W; a.depths = depths; a.R = R;
     return run(env, a);
 }
 
@@ -365,21 +369,48 @@ static int tl_intensity(const pgr_env* env, TlArgs a, double* out, void* stream,
     return tube_run(env, a, TL_TUBES, pgr_tl_bounds, nullptr, 0, (hipStream_t)stream, who, pgr_tl_sum);
 }
 
+// the two entries and their weighted twins (`who`: the entry named in errors)
+static int tl_fan_intensity(pgr_fan* f, const double* p0, const double* W, const double* depths, int64_t n_depths, double* out,
+                            void* stream, const char* who)
+{
+    return tl_fan_entry(f, p0, W, depths, n_depths, out, who, tl_no_check,
+                        [&](const pgr_env* e, TlArgs a) { return tl_intensity(e, a, out, stream, who); });
+}
+
+static int tl_buffer_intensity(pgr_env* env, const double* z, const double* p, int64_t n_rays, int32_t n_samples,
+                               const double* x, const double* p0, const double* W, const double* depths, int64_t n_depths,
+                               double* out, void* stream, const char* who)
+{
+    return tl_buffer_entry<false>(env, nullptr, z, p, n_rays, n_samples, x, p0, W, depths, n_depths, out, who, tl_no_check,
+                                  [&](const pgr_env* e, TlArgs a) { return tl_intensity(e, a, out, stream, who); });
+}
+
 extern "C" int pgr_fan_intensity(pgr_fan* f, const double* p0, const double* depths, int64_t n_depths, double* out,
                                  void* stream)
 {
-    const char* who = "pgr_fan_intensity";
-    return tl_fan_entry(f, p0, depths, n_depths, out, who, tl_no_check,
-                        [&](const pgr_env* e, TlArgs a) { return tl_intensity(e, a, out, stream, who); });
+    return tl_fan_intensity(f, p0, nullptr, depths, n_depths, out, stream, "pgr_fan_intensity");
+}
+
+extern "C" int pgr_fan_intensity_w(pgr_fan* f, const double* p0, const double* weights, const double* depths,
+                                   int64_t n_depths, double* out, void* stream)
+{
+    return tl_fan_intensity(f, p0, weights, depths, n_depths, out, stream, "pgr_fan_intensity_w");
 }
 
 extern "C" int pgr_intensity_device(pgr_env* env, const double* z, const double* p, int64_t n_rays, int32_t n_samples,
                                     const double* x, const double* p0, const double* depths, int64_t n_depths, double* out,
                                     void* stream)
 {
-    const char* who = "pgr_intensity_device";
-    return tl_buffer_entry<false>(env, nullptr, z, p, n_rays, n_samples, x, p0, depths, n_depths, out, who, tl_no_check,
-                                  [&](const pgr_env* e, TlArgs a) { return tl_intensity(e, a, out, stream, who); });
+    return tl_buffer_intensity(env, z, p, n_rays, n_samples, x, p0, nullptr, depths, n_depths, out, stream,
+                               "pgr_intensity_device");
+}
+
+extern "C" int pgr_intensity_device_w(pgr_env* env, const double* z, const double* p, int64_t n_rays, int32_t n_samples,
+                                      const double* x, const double* p0, const double* weights, const double* depths,
+                                      int64_t n_depths, double* out, void* stream)
+{
+    return tl_buffer_intensity(env, z, p, n_rays, n_samples, x, p0, weights, depths, n_depths, out, stream,
+                               "pgr_intensity_device_w");
 }
 
 #endif  // PGR_TL_H

@@ -34,6 +34,26 @@ def _save_grid(rays):
     return x
 
 
+def _absorption_profile(absorption):
+    """``absorption`` -> (depth nodes or None, alpha in dB per METRE), as the path kernels take them: a scalar in dB/km (a
+    constant profile), or a pair ``(depths_m, dB_per_km)`` of equal-length 1-D sequences, the depths strictly ascending.
+    dB/km -> dB/m is ``value / 1000.0``.  Everything that can be refused without a GPU is refused here."""
+    if isinstance(absorption, (tuple, list)) and len(absorption) == 2 and np.ndim(absorption[0]) == 1:
+        d, a = (np.asarray(v, dtype=float) for v in absorption)
+        if a.ndim != 1 or len(a) != len(d) or len(d) == 0:
+            raise ValueError("absorption = (depths_m, dB_per_km) needs two 1-D sequences of equal, non-zero length")
+        if not np.all(np.isfinite(d)) or not np.all(np.diff(d) > 0):
+            raise ValueError("absorption depths must be finite and strictly ascending")
+    else:
+        d, a = None, np.asarray(absorption, dtype=float)
+        if a.ndim != 0:
+            raise ValueError("absorption must be a scalar in dB/km or a pair (depths_m, dB_per_km)")
+        a = a.reshape(1)
+    if not np.all(np.isfinite(a)) or np.any(a < 0):
+        raise ValueError("absorption must be finite and >= 0 dB/km")
+    return (None if d is None else np.ascontiguousarray(d)), np.ascontiguousarray(a / 1000.0)
+
+
 class _TracedFan:
     """A fan (host or device resident) on its save ranges x, and -- after ``to_device`` -- the frame it was traced in: xf
     (mirrored for a backwards fan), the EnvHandle and its tables (cin, rin, zin), the torch stream and the fan's device
@@ -70,6 +90,20 @@ class _TracedFan:
             self._host[name] = self.upload(a)
         return self._host[name].data_ptr()
 
+    def path_integral(self, a_depths, alpha):
+        """The running path integral A (S, M) of the fan's rays, a float64 device tensor (csrc/pgr_path.h): alpha in dB/m on
+        the depth nodes a_depths (None with one alpha).  A device-resident fan is read where it is; a host fan's ts and zs
+        are uploaded (once per frame)."""
+        import torch
+        S, M = len(self.x), len(self.rays)
+        out = torch.empty((S, M), dtype=torch.float64, device=self.dev)
+        if self.handle is not None:
+            self.handle.path_integral(a_depths, alpha, out.data_ptr(), self.stream)
+        else:
+            _lib.path_integral_device(self.env, self._host_fan("ts"), self._host_fan("zs"), M, S, self._host_fan("xf"),
+                                      a_depths, alpha, out.data_ptr(), self.stream)
+        return out
+
 
 class _FanFrame(_TracedFan):
     """A fan checked for the tube kernels (`who` names the caller in errors): the receiver depths, the save ranges x and the
@@ -100,16 +134,29 @@ class _FanFrame(_TracedFan):
         self.p0 = _initial_slowness(self.rays.thetas, c_source)
         self.d_p0 = self.upload(self.p0)
         self.d_depths = self.upload(self.depths)
+        self.d_W = None
+        return self
+
+    def absorb(self, profile):
+        """Volume absorption for the entries ``run`` calls from here on: the path integral of the profile (from
+        _absorption_profile) runs once and becomes, in place, the weights W = 10^(-A / 10) of g, one trajectory array in
+        size, freed with this frame.  None: no weights, the unweighted entries."""
+        if profile is not None:
+            A = self.path_integral(*profile)
+            _lib.absorption_weights_device(self.env.device, A.data_ptr(), A.numel(), A.data_ptr(), self.stream)
+            self.d_W = A
         return self
 
     def run(self, entry, *args):
         """Tube entry `entry` on the fan, with p0, the arguments after it and the stream: ``FanHandle.<entry>`` on a
         device-resident fan, else ``_lib.<entry>_device`` on the host fan's trajectories (ts only for ``arrivals``)."""
         args = (self.d_p0.data_ptr(),) + args + (self.stream,)
+        # (the arrival counts have no weighted twin: finite weights leave the tubes counted as they are)
+        kw = {"weights": self.d_W.data_ptr()} if self.d_W is not None and entry != "arrival_counts" else {}
         if self.handle is not None:
-            return getattr(self.handle, entry)(*args)
+            return getattr(self.handle, entry)(*args, **kw)
         fan = [self._host_fan(k) for k in (("ts", "zs", "ps") if entry == "arrivals" else ("zs", "ps"))]
-        getattr(_lib, entry + "_device")(self.env, *fan, len(self.rays), len(self.x), self._host_fan("xf"), *args)
+        getattr(_lib, entry + "_device")(self.env, *fan, len(self.rays), len(self.x), self._host_fan("xf"), *args, **kw)
 
     def image(self):
         """an empty (R, S) float64 device array: an intensity image's output"""
@@ -134,7 +181,7 @@ def _db(out, intensity):
         return -10.0 * np.log10(I)
 
 
-def transmission_loss(rays, receiver_depths, environment, flatearth=True, device=0, intensity=False):
+def transmission_loss(rays, receiver_depths, environment, flatearth=True, device=0, intensity=False, absorption=None):
     """Incoherent ray-tube transmission loss of ``rays`` (a ``RayFan`` from ``shoot_rays``) at ``receiver_depths`` (metres,
     positive down, strictly ascending) on the fan's save ranges -> ndarray ``(len(receiver_depths), S)``:
     ``-10 log10(I)`` dB re 1 m (``+inf`` where no ray tube reaches, NaN in the source's own column), or ``I`` itself with
@@ -146,14 +193,23 @@ def transmission_loss(rays, receiver_depths, environment, flatearth=True, device
     incoherent, perfect boundary reflection; the sound speed is the bilinear look-up in the environment the fan was traced
     in (``environment`` with ``flatearth`` -- flat-earth depths, as the fan's ``zs`` -- and the mirrored frame of a
     backwards fan).  Known artefacts of the method: spikes at caustics and a strip about one tube wide along the surface
-    and the bottom.  A device-resident fan is processed where it is and stays device resident."""
-    f = _FanFrame(rays, receiver_depths, environment, flatearth, "transmission_loss").to_device(device)
+    and the bottom.  A device-resident fan is processed where it is and stays device resident.
+
+    ``absorption`` (default None: none, exactly the call without it): volume absorption along the ray paths, a scalar in
+    dB/km (``thorp_absorption(f)``) or a pair ``(depths_m, dB_per_km)`` (depths positive down, strictly ascending, in the
+    frame's depths as ``receiver_depths``; linear between the nodes, held outside them).  Every ray's g is then weighted by
+    10^(-A / 10), A the ray's running loss in dB (``path_loss``), so a tube carries the mean of its two rays' weighted g.
+    The weights are one trajectory array on the device for the duration of the call: 0.8 GB for 1e5 rays x 1001 samples,
+    8 GB at 1e6 rays."""
+    profile = None if absorption is None else _absorption_profile(absorption)
+    f = _FanFrame(rays, receiver_depths, environment, flatearth, "transmission_loss").to_device(device).absorb(profile)
     out = f.image()
     f.run("intensity", f.d_depths.data_ptr(), len(f.depths), out.data_ptr())
     return _db(out, intensity)
 
 
-def beam_transmission_loss(rays, receiver_depths, environment, flatearth=True, device=0, intensity=False, min_width=10.0):
+def beam_transmission_loss(rays, receiver_depths, environment, flatearth=True, device=0, intensity=False, min_width=10.0,
+                           absorption=None):
     """Incoherent Gaussian-beam transmission loss of ``rays`` (a ``RayFan`` from ``shoot_rays``) at ``receiver_depths``
     (metres, positive down, strictly ascending) on the fan's save ranges -> ndarray ``(len(receiver_depths), S)``:
     ``-10 log10(I)`` dB re 1 m (``+inf`` where no beam reaches, NaN in the source's own column), or ``I`` itself with
@@ -175,11 +231,15 @@ def beam_transmission_loss(rays, receiver_depths, environment, flatearth=True, d
     wavelength c / f.  Incoherent, perfect boundary reflection; the sound speed and bathymetry are those of the environment
     the fan was traced in (``environment`` with ``flatearth``; the mirrored frame of a backwards fan).  Unlike the top hat,
     no spikes at caustics and no strip along the boundaries; receivers outside [0, b] get what the formula gives.  A
-    device-resident fan is processed where it is and stays device resident."""
+    device-resident fan is processed where it is and stays device resident.
+
+    ``absorption``: volume absorption as in ``transmission_loss`` (E_k takes the weighted g; None, the default, runs
+    exactly the call without it; one trajectory array of device memory for the duration of the call)."""
     w = float(min_width)
     if not (np.isfinite(w) and w > 0):
         raise ValueError("min_width must be finite and > 0")
-    f = _FanFrame(rays, receiver_depths, environment, flatearth, "beam_transmission_loss").to_device(device)
+    profile = None if absorption is None else _absorption_profile(absorption)
+    f = _FanFrame(rays, receiver_depths, environment, flatearth, "beam_transmission_loss").to_device(device).absorb(profile)
     out, d_b = f.image(), f.upload(f.bottom())
     f.run("beam_intensity", d_b.data_ptr(), f.d_depths.data_ptr(), len(f.depths), w, out.data_ptr())
     return _db(out, intensity)
