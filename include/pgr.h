@@ -507,6 +507,61 @@ int pgr_debug_step(pgr_env* env, const double* t, const double* y, const double*
  * 3 quadratic estimate + three nodes, 4 dz = 1, 5 cubic estimate; SAVE: 0 end state, 1 trajectories (linspace grid, default sample
  * form), 2 any grid / PGR_EXACT_SAMPLES, 3 sample-blocked; PERSIST: persistent waves + packet queue.  -1s before any launch. */
 int pgr_debug_last_instance(const pgr_env* env, int32_t out[8]);
+/* LOG of that instance: 1 when it writes a bounce log (pgr_fan_launch_log), 0 when not; -1 before any launch or for a NULL env.
+ * (An entry of its own: the eight slots above are taken.) */
+int pgr_debug_last_instance_log(const pgr_env* env);
+
+/* ---- The bounce log of a fan and boundary reflection loss ----
+ *
+ * pgr_fan_launch_log: pgr_fan_launch, whose arguments it takes, with a log of max_bounces (>= 1) slots per ray.  Whenever the
+ * kernel applies a surface or bottom bounce to ray n, the ray's e-th (e = n_bott + n_surf before the bounce, counted from 0),
+ * it writes slot [e][n] of three arrays the handle owns (pgr_fan_destroy frees them):
+ *   bx (float64)  the range of the bounce: the located event abscissa, from which the next segment starts;
+ *   bp (float64)  the slowness the next segment starts with, sin(radians(theta_bounce)) / c, in the sign of the fan's
+ *                 trajectories (negated with PGR_STORED_SIGN);
+ *   bk (int8)     0 surface, 1 bottom.
+ * Events with e >= max_bounces are not written (n_bott / n_surf count on, so the overflow shows at the ray's end); slots never
+ * written hold NaN, NaN, -1.  A bounce that ends the ray (bounced backwards, bottom angle outside the table) is not logged.
+ * The integration never reads the log: status, counts, steps, end states and samples are those of pgr_fan_launch, bit for
+ * bit.  Needs trajectories (num_range_save >= 1) without PGR_EXACT_SAMPLES, on an environment whose fans run the LDS-table
+ * kernel or the sample-blocked one (PGR_OPT_API_BLOCKED on, the default); anything else is an error and nothing is launched.
+ *
+ * pgr_fan_fetch_bounces: bx, bp, bk (HOST, [max_bounces][M], NULL: not wanted) of the SURVIVING rays in launch order.  An
+ * error on a fan without a log.
+ *
+ * pgr_fan_boundary_loss / pgr_boundary_loss_device: the loss in dB every ray has collected at its bounces up to every save
+ * range.  For event e of ray m, with p = bp in the ODE sign (bp negated when stored):
+ *   c_e     the bilinear sound speed of pgr_fan_intensity at (bx_e, d_b), d_b = 0 at the surface and, at the bottom, the
+ *           environment's bottom depth at bx_e (linear in depths / depth_ranges, as the fan kernel evaluates it);
+ *   theta_e = asin(p c_e) (correctly rounded) times 180 / pi;
+ *   phi_e   = |theta_e| at the surface, |theta_e - beta(bx_e)| at the bottom, beta the table beta_deg on beta_x;
+ *   loss_e  = the table bot_db on g_deg (bottom) or surf_db on s_deg (surface) at phi_e.
+ * A table of n entries: n == 1 the constant (nodes may be NULL), else the interpolation rule of pgr_fan_path_integral (held
+ * at the end values outside the strictly ascending nodes, linear with a correctly rounded weight in between).  A NaN in bx,
+ * bp, theta (|p c| > 1) gives a NaN loss.  With x_s the save ranges np.linspace gives and E the ray's logged events (the
+ * leading slots whose bk is not -1; their bx must not decrease, as a fan's do not):
+ *   j_e = argmin_s |x_s - bx_e| (first minimum; 0 when bx_e is not finite),
+ *   seg(s) = #{e < E : j_e <= s} for s < S - 1, seg(S - 1) = E     (the samples the reference's _interpolate_ray gives a segment),
+ *   out_db[s * M + m] = sum of loss_e, e < seg(s), from 0.0 in increasing e;   nb / ns[s * M + m] = those events by kind.
+ * out_db (DEVICE float64 [S][M]), nb, ns (DEVICE int32 [S][M], NULL: not wanted): every entry is written.  One lane forms each
+ * ray's sum in order: no atomics, repeated calls are bit-equal.  The tables are HOST arrays, checked before any device work
+ * (dB values finite and >= 0, beta finite, nodes finite and strictly ascending, n >= 1, out_db not NULL).  Enqueued on
+ * `stream`; returns without synchronising.
+ * pgr_fan_boundary_loss: a fan of pgr_fan_launch_log (waits for its kernel; dropped rays are skipped in place).
+ * pgr_boundary_loss_device: caller buffers bx, bp, bk (DEVICE, [K][n_rays], stored sign, every ray kept) on the save ranges
+ *   np.linspace(x0, x1, n_samples) in the frame of `env`. */
+int pgr_fan_launch_log(pgr_env* env, const double* y0, const double* ode_angles_deg, double source_depth, double c_source,
+                       int64_t N, double source_range, double receiver_range, int32_t num_range_save, double rtol,
+                       double atol, uint32_t flags, int64_t max_steps, int32_t max_bounces, pgr_fan** out);
+int pgr_fan_fetch_bounces(pgr_fan* fan, double* bx, double* bp, int8_t* bk);
+int pgr_fan_boundary_loss(pgr_fan* fan, const double* g_deg, const double* bot_db, int32_t n_bot, const double* s_deg,
+                          const double* surf_db, int32_t n_surf_tab, const double* beta_x, const double* beta_deg,
+                          int32_t n_beta, double* out_db, int32_t* nb, int32_t* ns, void* stream);
+int pgr_boundary_loss_device(pgr_env* env, const double* bx, const double* bp, const int8_t* bk, int64_t n_rays, int32_t K,
+                             double x0, double x1, int32_t n_samples, const double* g_deg, const double* bot_db,
+                             int32_t n_bot, const double* s_deg, const double* surf_db, int32_t n_surf_tab,
+                             const double* beta_x, const double* beta_deg, int32_t n_beta, double* out_db, int32_t* nb,
+                             int32_t* ns, void* stream);
 
 /* What this build of the library is: whether the instruction-layout pass of the build was applied
  * ("relaid: 502 -> 31 straddles ..." or "plain hipcc") and which arithmetic variant was compiled.

@@ -8,13 +8,14 @@ needs ``libpgr_hip.so`` and a GPU.
 """
 from .xr_lite import DataArray
 from .environment import OceanEnvironment2D, munk_ssp, eflat, eflatinv, flat_earth_c
-from .ray_objects import Ray, RayFan, TimeFront, EigenRays
+from .ray_objects import Ray, RayFan, BounceLog, TimeFront, EigenRays
 from .launch_rays import shoot_rays, shoot_ray, _unpack_envi
 from .eigenrays import find_eigenrays
 from .transmission import transmission_loss, beam_transmission_loss
 from .arrivals import arrivals, Arrivals
 from .sensitivity import travel_time_kernel
 from .absorption import thorp_absorption, path_length, path_loss
+from .boundary import boundary_loss
 from .host_physics import (derivsrd, bottom_bounce, surface_bounce, ray_bounding_box_event,
                            ray_angle, bilinear_interp, linear_interp, vertical_ray)
 from . import _lib
@@ -25,6 +26,6 @@ ARITHMETIC = _lib.ARITH
 
 __all__ = ["OceanEnvironment2D", "munk_ssp", "eflat", "eflatinv", "flat_earth_c", "DataArray", "Ray", "RayFan", "TimeFront",
            "EigenRays", "shoot_rays", "shoot_ray", "find_eigenrays", "transmission_loss", "beam_transmission_loss", "arrivals", "Arrivals",
-           "travel_time_kernel", "thorp_absorption", "path_length", "path_loss", "derivsrd", "bottom_bounce",
+           "travel_time_kernel", "thorp_absorption", "path_length", "path_loss", "boundary_loss", "BounceLog", "derivsrd", "bottom_bounce",
            "surface_bounce", "ray_bounding_box_event", "ray_angle", "bilinear_interp",
            "linear_interp", "vertical_ray"]

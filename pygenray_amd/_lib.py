@@ -263,7 +263,15 @@ def load():
             ("pgr_fan_arrivals_w", [_vp, _vp, _vp, _vp, _i64, _vp, i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
             ("pgr_intensity_device_w", [_vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
             ("pgr_beam_intensity_device_w", [_vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _vp, _vp, _i64, f64, _vp, _vp]),
-            ("pgr_arrivals_device_w", [_vp, _vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _vp, _i64, _vp, i32, _vp, _i64] + [_vp] * 6)):
+            ("pgr_arrivals_device_w", [_vp, _vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _vp, _i64, _vp, i32, _vp, _i64] + [_vp] * 6),
+            # the bounce log and boundary reflection loss (csrc/pgr_bounce.h)
+            ("pgr_fan_launch_log", [_vp, _vp, _vp, f64, f64, _i64, f64, f64, i32, f64, f64, ctypes.c_uint32, _i64, i32,
+                                    ctypes.POINTER(_vp)]),
+            ("pgr_fan_fetch_bounces", [_vp, _vp, _vp, _vp]),
+            ("pgr_fan_boundary_loss", [_vp, _vp, _vp, i32, _vp, _vp, i32, _vp, _vp, i32, _vp, _vp, _vp, _vp]),
+            ("pgr_boundary_loss_device", [_vp, _vp, _vp, _vp, _i64, i32, f64, f64, i32, _vp, _vp, i32, _vp, _vp, i32, _vp, _vp, i32,
+                                          _vp, _vp, _vp, _vp]),
+            ("pgr_debug_last_instance_log", [_vp])):
         getattr(L, name).restype = ctypes.c_int
         getattr(L, name).argtypes = argtypes
     _lib = L
@@ -453,6 +461,11 @@ class EnvHandle:
         check(L.pgr_debug_last_instance(self._h, out))
         return dict(zip(("lds_tab", "zm", "save", "persist", "blocks", "threads", "lds_bytes", "queue_tail"), (int(v) for v in out)))
 
+    def last_instance_log(self):
+        """pgr_debug_last_instance_log: 1 when the last fan launch selected an instance that writes a bounce log, 0 when not,
+        -1 before any launch."""
+        return int(load().pgr_debug_last_instance_log(self._h))
+
     def eval_points(self, x, y):
         x = _c(x); y = _c(y).reshape(-1, 3)
         out = np.empty((len(x), 10))
@@ -466,7 +479,9 @@ class FanHandle:
 
     def __init__(self, env, x0, x1, S, y0=None, ode_angles_deg=None, source_depth=0.0, c_source=1.0, rtol=1e-9,
                  atol=1e-6, terminate_backwards=True, max_steps=1_000_000, stored_sign=False, exact_samples=False,
-                 exact_bisection=False, p0=None, skip_nan=False):
+                 exact_bisection=False, p0=None, skip_nan=False, max_bounces=None):
+        """``max_bounces`` (an int >= 1; None: no log, pgr_fan_launch as ever): pgr_fan_launch_log -- the fan keeps a bounce
+        log of that many slots per ray (``fetch_bounces``, ``boundary_loss``)."""
         L = load()
         L.pgr_fan_launch.restype = ctypes.c_int
         L.pgr_fan_launch.argtypes = [_vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _i64, ctypes.c_double, ctypes.c_double,
@@ -494,11 +509,33 @@ class FanHandle:
             (PGR_EXACT_SAMPLES if exact_samples else 0) | (PGR_EXACT_BISECTION if exact_bisection else 0) | \
             (PGR_LAUNCH_SLOWNESS if p0 is not None else 0) | (PGR_SKIP_NAN_Y0 if skip_nan else 0)
         h = _vp()
-        check(L.pgr_fan_launch(env._h, _vptr(y0), _vptr(ode_angles_deg), float(source_depth), float(c_source), n,
-                               float(x0), float(x1), self.S, float(rtol), float(atol), flags, int(max_steps),
-                               ctypes.byref(h)))
+        self.K = 0 if max_bounces is None else int(max_bounces)
+        if max_bounces is None:
+            check(L.pgr_fan_launch(env._h, _vptr(y0), _vptr(ode_angles_deg), float(source_depth), float(c_source), n,
+                                   float(x0), float(x1), self.S, float(rtol), float(atol), flags, int(max_steps),
+                                   ctypes.byref(h)))
+        else:
+            check(L.pgr_fan_launch_log(env._h, _vptr(y0), _vptr(ode_angles_deg), float(source_depth), float(c_source), n,
+                                       float(x0), float(x1), self.S, float(rtol), float(atol), flags, int(max_steps),
+                                       self.K, ctypes.byref(h)))
         self._h = h
         self.M = None
+
+    def fetch_bounces(self):
+        """pgr_fan_fetch_bounces: the bounce log of the surviving rays -> x, p (K, M) float64 and kind (K, M) int8; slots
+        never written hold NaN, NaN, -1."""
+        if self.M is None:
+            self.wait()
+        x, p = np.empty((self.K, self.M)), np.empty((self.K, self.M))
+        k = np.empty((self.K, self.M), np.int8)
+        check(load().pgr_fan_fetch_bounces(self._h, _vptr(x), _vptr(p), _vptr(k)))
+        return x, p, k
+
+    def boundary_loss(self, tables, out_ptr, nb_ptr=0, ns_ptr=0, stream=0):
+        """pgr_fan_boundary_loss: out[S][M] (device pointer) = the boundary loss in dB of this fan's surviving rays up to
+        every save range; `tables` = boundary_tables(...) (host); nb / ns [S][M] int32 device pointers or 0."""
+        check(load().pgr_fan_boundary_loss(self._h, *_table_args(tables), _vp(out_ptr), _vp(nb_ptr or None), _vp(ns_ptr or None),
+                                           _vp(stream or None)))
 
     def wait(self):
         n, m = _i64(0), _i64(0)
@@ -786,6 +823,35 @@ def path_integral_device(env, t_ptr, z_ptr, n_rays, n_samples, x_ptr, a_depths, 
         raise ValueError("a_depths and alpha must have equal length")
     check(load().pgr_path_integral_device(env._h, _vp(t_ptr), _vp(z_ptr), int(n_rays), int(n_samples), _vp(x_ptr), _vptr(ad),
                                           _vptr(al), len(al), _vp(out_ptr), _vp(stream or None)))
+
+
+def boundary_tables(bottom, surface, beta):
+    """Three (nodes or None, values) pairs -> the host arrays pgr_fan_boundary_loss / pgr_boundary_loss_device take (kept
+    alive by the returned tuple): the bottom loss on grazing angles, the surface loss, the bottom slope in degrees on ranges."""
+    out = []
+    for nodes, values in (bottom, surface, beta):
+        v = _c(values).reshape(-1)
+        x = None if nodes is None else _c(nodes).reshape(-1)
+        if x is not None and len(x) != len(v):
+            raise ValueError("a table's nodes and values must have equal length")
+        out.append((x, v))
+    return tuple(out)
+
+
+def _table_args(tables):
+    args = []
+    for x, v in tables:
+        args += [_vptr(x), _vptr(v), len(v)]
+    return args
+
+
+def boundary_loss_device(env, bx_ptr, bp_ptr, bk_ptr, n_rays, K, x0, x1, n_samples, tables, out_ptr, nb_ptr=0, ns_ptr=0,
+                         stream=0):
+    """pgr_boundary_loss_device on raw device pointers (ints): the log bx, bp (float64) and bk (int8), [K][n_rays] each, stored
+    sign, on the save ranges np.linspace(x0, x1, n_samples) of the frame of `env`."""
+    check(load().pgr_boundary_loss_device(env._h, _vp(bx_ptr), _vp(bp_ptr), _vp(bk_ptr), int(n_rays), int(K), float(x0),
+                                          float(x1), int(n_samples), *_table_args(tables), _vp(out_ptr), _vp(nb_ptr or None),
+                                          _vp(ns_ptr or None), _vp(stream or None)))
 
 
 def absorption_weights_device(device, a_ptr, n, w_ptr, stream=0):

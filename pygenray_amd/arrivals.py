@@ -7,7 +7,7 @@ already are -- in HBM for a device-resident fan, uploaded through torch for a ho
 import numpy as np
 
 from .ray_objects import _columns
-from .transmission import _FanFrame, _absorption_profile
+from .transmission import _FanFrame, _absorption_profile, _boundary_spec
 
 
 def _bilinear(x, y, x_grid, y_grid, values):
@@ -118,7 +118,8 @@ class Arrivals:
                 f"{len(self.range_indices)} ranges)")
 
 
-def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=None, device=0, absorption=None):
+def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=None, device=0, absorption=None,
+             bottom_loss=None, surface_loss=None):
     """Ray-tube arrivals of ``rays`` (a ``RayFan`` from ``shoot_rays``) at ``receiver_depths`` (metres, positive down,
     strictly ascending) and the save columns ``range_indices`` (default ``[S - 1]``, the receiver range; any integers in
     -S .. S - 1) -> ``Arrivals``.
@@ -131,12 +132,16 @@ def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=N
     ``absorption``: volume absorption as in ``transmission_loss`` -- ``intensity`` (and ``amplitude``, its square root) is
     the weighted tube's term, which still adds up to the weighted ``transmission_loss`` bit for bit; the arrivals found,
     their order, times and slownesses do not change.  None (default) runs exactly the call without it; the weights take
-    one trajectory array of device memory for the duration of the call."""
+    one trajectory array of device memory for the duration of the call.
+
+    ``bottom_loss`` / ``surface_loss``: boundary reflection loss as in ``transmission_loss``, one more factor of the same
+    weights (None and None, the default: exactly the call without them; a fan with a bounce log otherwise)."""
     profile = None if absorption is None else _absorption_profile(absorption)
+    boundary = _boundary_spec(rays, bottom_loss, surface_loss)
     f = _FanFrame(rays, receiver_depths, environment, flatearth, "arrivals")
     S = len(f.x)
     cols = _columns(range_indices, S)
-    f.to_device(device).absorb(profile)
+    f.to_device(device).absorb(profile, boundary)
     import torch
 
     R, n = len(f.depths), len(cols)

@@ -84,6 +84,18 @@ struct FanArgs {
     int n_queue_tail;     // the last n_queue_tail entries are the FIRST packets of the workgroups' waves 4 .. 7 (4 per workgroup), not queued
 };
 
+// The arguments of the fan-kernel instances that write a bounce log (pgr_fan_kernel<..., LOG = true>): FanArgs, unchanged and
+// first, then the log -- slot [e][ray] for a ray's e-th bounce, e < log_K.  The instances without a log
+// take FanArgs itself.
+struct FanArgsLog : FanArgs {
+    double* log_x;         // [log_K][N] range of the bounce
+    double* log_p;         // [log_K][N] slowness the next segment starts with (stored sign with PGR_STORED_SIGN)
+    signed char* log_k;    // [log_K][N] 0 surface, 1 bottom
+    int32_t log_K;
+};
+template <bool LOG> struct FanKernelArgs { typedef FanArgs type; };
+template <> struct FanKernelArgs<true> { typedef FanArgsLog type; };
+
 // The fan kernel's service phase and epilogue re-read FanArgs from the kernel-argument segment (so that what only they
 // need does not sit in SGPRs across the step loop): it is the kernel's SECOND argument, behind one pointer.
 constexpr int kFanArgsKernargOffset = 8;

@@ -69,6 +69,10 @@ struct pgr_fan {
     size_t scratch_bytes = 0;
     int* d_keep = nullptr;  // the surviving rays' columns on the device (pgr_fan_intensity, pgr_tl.h): uploaded once, freed with the handle
     bool r_filled = false;  // `r` holds the save ranges (pgr_fan_intensity fills it on first use)
+    // the bounce log of pgr_fan_launch_log: x, p [K][N] doubles and kind [K][N] int8 in one allocation of
+    // the handle's own, freed with it; K == 0: a fan without a log
+    void* log_buf = nullptr;
+    FanLog log{};
     std::mutex m;
 };
 
@@ -80,6 +84,7 @@ extern "C" void pgr_fan_destroy(pgr_fan* f)
     if (f->done) { (void)hipEventSynchronize(f->done); (void)hipEventDestroy(f->done); }
     if (f->scratch) (void)hipFree(f->scratch);
     if (f->d_keep) (void)hipFree(f->d_keep);
+    if (f->log_buf) (void)hipFree(f->log_buf);
     bool last = false;
     {
         std::lock_guard<std::mutex> lock(env->fan_pool_mutex);
@@ -95,12 +100,24 @@ extern "C" void pgr_fan_destroy(pgr_fan* f)
     if (last) env_release(env);   // pgr_env_destroy came first: the environment goes with its last fan
 }
 
-extern "C" int pgr_fan_launch(pgr_env* env, const double* y0, const double* ode_angles_deg, double source_depth,
-                              double c_source, int64_t N, double source_range, double receiver_range, int32_t S,
-                              double rtol, double atol, uint32_t flags, int64_t max_steps, pgr_fan** out)
+// pgr_fan_launch and, with max_bounces >= 1, pgr_fan_launch_log
+static int fan_launch(pgr_env* env, const double* y0, const double* ode_angles_deg, double source_depth,
+                      double c_source, int64_t N, double source_range, double receiver_range, int32_t S,
+                      double rtol, double atol, uint32_t flags, int64_t max_steps, int32_t max_bounces, pgr_fan** out)
 {
     if (!env || !out) return fail("pgr_fan_launch: null argument");
     *out = nullptr;
+    if (max_bounces < 0 || (max_bounces > 0 && S < 1)) return fail("pgr_fan_launch_log: need max_bounces >= 1 and trajectories (num_range_save >= 1)");
+    if (max_bounces > 0 && (flags & PGR_EXACT_SAMPLES)) return fail("pgr_fan_launch_log: no bounce log with PGR_EXACT_SAMPLES");
+    if (max_bounces > 0) {
+        // (what pgr_shoot_fan_device would refuse, refused before the upload of y0 is queued)
+        bool lds_tab;
+        int zm;
+        size_t zx_bytes;
+        select_variant(env, lds_tab, zm, zx_bytes);
+        if (!lds_tab && !blocked_layout_fits(env))
+            return fail("pgr_fan_launch_log: no bounce log for rows on tables in HBM (PGR_OPT_API_BLOCKED off, or no LDS left for the sample-blocked layout)");
+    }
     const double t0 = trace_now();
     if (N <= 0) return fail("pgr_fan_launch: need at least one ray");
     if (!y0 && !ode_angles_deg) return fail("pgr_fan_launch: give y0 or launch angles");
@@ -135,6 +152,22 @@ extern "C" int pgr_fan_launch(pgr_env* env, const double* y0, const double* ode_
     if (!grow_buffer(f->buf, f->buf_bytes, total)) { pgr_fan_destroy(f); return fail("pgr_fan_launch: device allocation failed"); }
     f->d = fan_carve(f->buf, N, S, f->save, f->blocked);
     hipStream_t st = f->stream;
+    if (max_bounces > 0) {
+        // x | p | kind, each piece 256-byte aligned; never-written slots keep the fill: all-ones bytes are NaN, NaN, -1
+        const size_t kn = (size_t)max_bounces * (size_t)N, piece = (kn * 8 + 255) & ~(size_t)255;
+        const size_t bytes = 2 * piece + ((kn + 255) & ~(size_t)255);
+        if (hipMalloc(&f->log_buf, bytes) != hipSuccess) {
+            f->log_buf = nullptr;
+            (void)hipGetLastError();
+            pgr_fan_destroy(f);
+            return fail("pgr_fan_launch_log: device allocation of the bounce log failed");
+        }
+        f->log.x = (double*)f->log_buf;
+        f->log.p = (double*)((char*)f->log_buf + piece);
+        f->log.k = (signed char*)((char*)f->log_buf + 2 * piece);
+        f->log.K = max_bounces;
+        if (hipMemsetAsync(f->log_buf, 0xFF, bytes, st) != hipSuccess) { pgr_fan_destroy(f); return fail("pgr_fan_launch_log: fill of the bounce log"); }
+    }
     hipEvent_t up = nullptr;
     int rc = 0;
     do {
@@ -156,9 +189,9 @@ extern "C" int pgr_fan_launch(pgr_env* env, const double* y0, const double* ode_
             }
         }
         if (hipEventCreateWithFlags(&up, hipEventDisableTiming) != hipSuccess || hipEventRecord(up, st) != hipSuccess) { rc = fail("pgr_fan_launch: event"); break; }
-        rc = pgr_shoot_fan_device(env, f->d.y0, N, source_range, receiver_range, f->d.r, S > 0 ? S : 1, rtol, atol, f->flags, max_steps,
-                                  f->save ? f->d.T : nullptr, f->save ? f->d.Z : nullptr, f->save ? f->d.P : nullptr, f->d.end,
-                                  f->d.nb, f->d.ns, f->d.st, f->d.n1, f->d.n2, (void*)st);
+        rc = shoot_fan_device(env, f->d.y0, N, source_range, receiver_range, f->d.r, S > 0 ? S : 1, rtol, atol, f->flags, max_steps,
+                              f->save ? f->d.T : nullptr, f->save ? f->d.Z : nullptr, f->save ? f->d.P : nullptr, f->d.end,
+                              f->d.nb, f->d.ns, f->d.st, f->d.n1, f->d.n2, (void*)st, f->log);
         if (rc) break;
         if (hipEventRecord(f->done, st) != hipSuccess) { rc = fail("pgr_fan_launch: event record"); break; }
         // the caller may release y0 / the angles when this returns: wait for the upload (not for the kernel behind it)
@@ -169,6 +202,24 @@ extern "C" int pgr_fan_launch(pgr_env* env, const double* y0, const double* ode_
     *out = f;
     PGR_MARK(t0, "pgr_fan_launch: enqueued, upload done");
     return 0;
+}
+
+extern "C" int pgr_fan_launch(pgr_env* env, const double* y0, const double* ode_angles_deg, double source_depth,
+                              double c_source, int64_t N, double source_range, double receiver_range, int32_t S,
+                              double rtol, double atol, uint32_t flags, int64_t max_steps, pgr_fan** out)
+{
+    return fan_launch(env, y0, ode_angles_deg, source_depth, c_source, N, source_range, receiver_range, S, rtol, atol, flags,
+                      max_steps, 0, out);
+}
+
+extern "C" int pgr_fan_launch_log(pgr_env* env, const double* y0, const double* ode_angles_deg, double source_depth,
+                                  double c_source, int64_t N, double source_range, double receiver_range, int32_t S,
+                                  double rtol, double atol, uint32_t flags, int64_t max_steps, int32_t max_bounces, pgr_fan** out)
+{
+    if (out) *out = nullptr;
+    if (max_bounces < 1) return fail("pgr_fan_launch_log: max_bounces must be >= 1");
+    return fan_launch(env, y0, ode_angles_deg, source_depth, c_source, N, source_range, receiver_range, S, rtol, atol, flags,
+                      max_steps, max_bounces, out);
 }
 
 // waits for the kernel, reads the status array back once and counts the surviving rays
@@ -263,6 +314,35 @@ extern "C" int pgr_fan_fetch_rays_compact(pgr_fan* f, const double* per_ray_in, 
             if (m0 < m1) th.emplace_back(work, m0, m1);
         }
         for (auto& t : th) t.join();
+    }
+    return 0;
+}
+
+// The bounce log of the SURVIVING rays, in launch order: bx, bp [K][M] and bk [K][M] (NULL: not wanted).  The log is small
+// (17 bytes per slot): it comes over whole and is squeezed through the keep list on the host.
+extern "C" int pgr_fan_fetch_bounces(pgr_fan* f, double* bx, double* bp, int8_t* bk)
+{
+    if (!f) return fail("pgr_fan_fetch_bounces: null fan");
+    if (!f->log.K) return fail("pgr_fan_fetch_bounces: the fan was launched without a bounce log (pgr_fan_launch_log)");
+    std::lock_guard<std::mutex> lock(f->m);
+    HIPCHK(hipSetDevice(f->env->device));
+    int rc = fan_finish(f);
+    if (rc) return rc;
+    const size_t n = (size_t)f->N, M = (size_t)f->M, K = (size_t)f->log.K;
+    const int* keep = f->keep.data();
+    std::vector<double> h(bx || bp ? K * n : 0);
+    for (int which = 0; which < 2; which++) {
+        double* dst = which ? bp : bx;
+        if (!dst) continue;
+        HIPCHK(hipMemcpy(h.data(), which ? f->log.p : f->log.x, K * n * 8, hipMemcpyDeviceToHost));
+        for (size_t e = 0; e < K; e++)
+            for (size_t m = 0; m < M; m++) dst[e * M + m] = h[e * n + (size_t)keep[m]];
+    }
+    if (bk) {
+        std::vector<int8_t> hk(K * n);
+        HIPCHK(hipMemcpy(hk.data(), f->log.k, K * n, hipMemcpyDeviceToHost));
+        for (size_t e = 0; e < K; e++)
+            for (size_t m = 0; m < M; m++) bk[e * M + m] = hk[e * n + (size_t)keep[m]];
     }
     return 0;
 }

@@ -28,9 +28,13 @@
 // sample-blocked layout [ceil(S/4)][N][4] (PGR_SAMPLE_BLOCKED; instantiated for the HBM-table kernels only)
 // PERSIST: persistent waves claiming 64-ray packets from the cost-sorted list (fans of several rounds; see the packet loop
 // below); false: one packet per wave, and the loop folds away -- the instances the 1e5-ray fans run are the code they were
-template <bool LDS_TAB, int ZM, int SAVE, bool PERSIST>
+// LOG: the bounce log -- the service phase that applies a surface or bottom bounce writes the bounce's
+// range, reflected slowness and kind into slot [n_bott + n_surf][ray] of FanArgsLog's arrays.  Everything of it sits under
+// `if constexpr (LOG)` in the service phase, and the log's arguments ride BEHIND FanArgs (FanArgsLog), so the instances
+// without a log are the code they were.  The integration never reads the log.
+template <bool LDS_TAB, int ZM, int SAVE, bool PERSIST, bool LOG = false>
 __global__ void __launch_bounds__(512)
-pgr_fan_kernel(const EnvDev* __restrict__ env_p, FanArgs a)
+pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::type a)
 {
     // the environment descriptor lives in device memory: its ~50 dwords would otherwise occupy
     // half the wave's SGPRs as kernel arguments and push the Runge-Kutta tableau (60 fp64
@@ -792,6 +796,19 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, FanArgs a)
                                     // (theta_b = -theta at the surface and on a flat floor: the sine of minus an arcsine, cheaply)
                                     y2 = fdiv(pgr_cr_sin_near_minus_asin(theta_b * (M_PI / 180.0), pc_b, A_b), c);
                                     need_init = true;
+                                    if constexpr (LOG) {
+                                        // the bounce log: event e = n_bott + n_surf before this bounce was counted; a
+                                        // bounce that drops the ray (backwards, bottom angle out of range) is not logged
+                                        const FanArgsLog __attribute__((address_space(4))) & al =
+                                            *(const FanArgsLog __attribute__((address_space(4))) *)(ks_p + kFanArgsKernargOffset);
+                                        const int e = nb + ns - 1;
+                                        if (e < al.log_K) {
+                                            const int64_t o = (int64_t)e * as.N + ray;
+                                            al.log_x[o] = t;
+                                            al.log_p[o] = SGN(y2);
+                                            al.log_k[o] = (signed char)ev;
+                                        }
+                                    }
                                     if (!(t < t_bound)) status = PGR_RAY_OK;
                                     else if (n_steps > max_steps32) status = PGR_RAY_MAX_STEPS;
                                 }

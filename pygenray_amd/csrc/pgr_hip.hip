@@ -58,3 +58,4 @@
 #include "pgr_sens.h"           // travel-time sensitivity kernels: pgr_fan_travel_time_kernel, pgr_travel_time_kernel_device
 #include "pgr_front.h"          // time fronts and turning-point counts: pgr_fan_time_front, pgr_time_front_device
 #include "pgr_path.h"           // path integrals, absorption weights: pgr_fan_path_integral, pgr_path_integral_device
+#include "pgr_bounce.h"         // boundary reflection loss from a fan's bounce log: pgr_fan_boundary_loss, pgr_boundary_loss_device

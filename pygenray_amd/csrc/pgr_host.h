@@ -85,6 +85,7 @@ struct pgr_env {
     // the test that walks every instance asserts that it launched the one it meant to)
     // (atomics: two host threads may launch on one environment; the record is a diagnostic, each field is whole)
     std::atomic<int> last_instance[8];
+    std::atomic<int> last_instance_log{-1};   // LOG of that instance (pgr_debug_last_instance_log)
     pgr_env() { for (int q = 0; q < 8; q++) last_instance[q].store(q < 4 ? -1 : 0, std::memory_order_relaxed); }
 };
 

@@ -127,12 +127,20 @@ static bool fan_blocked(const pgr_env* env, bool save, uint32_t flags)
     return save && (flags & PGR_SAVE_LINSPACE) && (flags & PGR_SAMPLE_MAJOR) && !(flags & PGR_EXACT_SAMPLES) && blocked_layout_fits(env);
 }
 
-extern "C" int pgr_shoot_fan_device(pgr_env* env, const double* y0, int64_t N, double source_range,
-                                    double receiver_range, const double* r_save, int32_t S,
-                                    double rtol, double atol, uint32_t flags, int64_t max_steps,
-                                    double* T, double* z, double* p, double* end_state,
-                                    int32_t* n_bott, int32_t* n_surf, int32_t* status,
-                                    int32_t* n_steps, int32_t* n_rej, void* stream)
+// The bounce log of a launch: three [K][N] arrays the LOG instances of the fan kernel write; K == 0: none.
+struct FanLog {
+    double* x = nullptr;
+    double* p = nullptr;
+    signed char* k = nullptr;
+    int32_t K = 0;
+};
+
+static int shoot_fan_device(pgr_env* env, const double* y0, int64_t N, double source_range,
+                            double receiver_range, const double* r_save, int32_t S,
+                            double rtol, double atol, uint32_t flags, int64_t max_steps,
+                            double* T, double* z, double* p, double* end_state,
+                            int32_t* n_bott, int32_t* n_surf, int32_t* status,
+                            int32_t* n_steps, int32_t* n_rej, void* stream, const FanLog& log)
 {
     if (!env) return fail("pgr_shoot_fan: null env");
     if (N < 0) return fail("pgr_shoot_fan: negative ray count");
@@ -148,7 +156,8 @@ extern "C" int pgr_shoot_fan_device(pgr_env* env, const double* y0, int64_t N, d
     if (!(source_range < receiver_range)) return fail("pgr_shoot_fan: need source_range < receiver_range (mirror backwards shots)");
     HIPCHK(hipSetDevice(env->device));
 
-    FanArgs a{};
+    FanArgsLog a{};   // (the instances without a log take its FanArgs part)
+    a.log_x = log.x; a.log_p = log.p; a.log_k = log.k; a.log_K = log.K;
     a.y0 = y0; a.r_save = r_save; a.T = T; a.Z = z; a.P = p; a.end_state = end_state;
     a.n_bott = n_bott; a.n_surf = n_surf; a.status = status; a.n_steps = n_steps; a.n_rej = n_rej;
     a.N = N; a.S = save ? S : 1;
@@ -180,6 +189,16 @@ extern "C" int pgr_shoot_fan_device(pgr_env* env, const double* y0, int64_t N, d
         if (!save || !(flags & PGR_SAMPLE_MAJOR)) return fail("pgr_shoot_fan: PGR_SAMPLE_BLOCKED goes with trajectories and PGR_SAMPLE_MAJOR");
         if (lds_tab) return fail("pgr_shoot_fan: PGR_SAMPLE_BLOCKED is for environments whose tables stay in HBM (this one is on the LDS-table path)");
         if (!a.save_formula || (flags & PGR_EXACT_SAMPLES)) return fail("pgr_shoot_fan: PGR_SAMPLE_BLOCKED needs a linspace save grid (PGR_SAVE_LINSPACE) and the default sample form");
+    }
+    // the bounce log is instantiated where the API's trajectory fans run: rows with the LDS table (SAVE 1), sample-blocked with
+    // the tables in HBM (SAVE 3); refused here, before anything is queued
+    if (log.K) {
+        if (!log.x || !log.p || !log.k) return fail("pgr_shoot_fan: the bounce log needs its three arrays");
+        const bool rows_lds = save && lds_tab && !(flags & PGR_SAMPLE_BLOCKED) && (flags & PGR_SAVE_LINSPACE) && !(flags & PGR_EXACT_SAMPLES);
+        const bool blocked_hbm = save && !lds_tab && (flags & PGR_SAMPLE_BLOCKED);
+        if (!rows_lds && !blocked_hbm)
+            return fail("pgr_shoot_fan: a bounce log goes with trajectories on a linspace grid in the default sample form: rows with the "
+                        "LDS table, sample-blocked with the tables in HBM (not PGR_EXACT_SAMPLES, end states only, or PGR_OPT_API_BLOCKED off)");
     }
     // SAVE of the kernel instance: 0 end state only, 1 trajectories on a linspace grid (default sample form), 2 any grid /
     // PGR_EXACT_SAMPLES, 3 = 1 in the sample-blocked layout; persistent waves are instantiated for 0, 1 and 3
@@ -262,15 +281,23 @@ extern "C" int pgr_shoot_fan_device(pgr_env* env, const double* y0, int64_t N, d
     // tail entry n - 1 - (4 blockIdx + wave - 4) and never queues the tail): a change of either would skip or double-integrate packets
     if (a.n_queue_tail && !(threads == 512 && blocks * 4 == (int64_t)a.n_queue_tail))
         return fail("pgr_shoot_fan: internal error: the packet queue's pre-assigned tail does not match the launch shape");
-#define PGR_LAUNCH2(LT, ZMV, SV, PV)                                                                 \
+#define PGR_LAUNCH3(LT, ZMV, SV, PV, LG, ARGS)                                                       \
     do {                                                                                             \
         { const int li_[8] = {(int)(LT), (ZMV), (SV), (int)(PV), (int)blocks, threads, (int)lds, a.n_queue_tail};              \
           for (int q_ = 0; q_ < 8; q_++) env->last_instance[q_].store(li_[q_], std::memory_order_relaxed); } \
+        env->last_instance_log.store((int)(LG), std::memory_order_relaxed);                          \
         if (lds > 64 * 1024)                                                                         \
-            HIPCHK(hipFuncSetAttribute((const void*)pgr_fan_kernel<LT, ZMV, SV, PV>,                 \
+            HIPCHK(hipFuncSetAttribute((const void*)pgr_fan_kernel<LT, ZMV, SV, PV, LG>,             \
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));       \
-        hipLaunchKernelGGL((pgr_fan_kernel<LT, ZMV, SV, PV>), dim3((unsigned)blocks), dim3(threads), lds, \
-                           st, env->d_dev, a);                                                       \
+        hipLaunchKernelGGL((pgr_fan_kernel<LT, ZMV, SV, PV, LG>), dim3((unsigned)blocks), dim3(threads), lds, \
+                           st, env->d_dev, ARGS);                                                    \
+    } while (0)
+#define PGR_LAUNCH2(LT, ZMV, SV, PV) PGR_LAUNCH3(LT, ZMV, SV, PV, false, (static_cast<const FanArgs&>(a)))
+// the LOG instances: <LDS table, SAVE 1> and <HBM tables, SAVE 3>, both PERSIST values
+#define PGR_LAUNCH_LOG(LT, ZMV, SV)                                                                  \
+    do {                                                                                             \
+        if (a.wave_queue) PGR_LAUNCH3(LT, ZMV, SV, true, true, a);                                   \
+        else PGR_LAUNCH3(LT, ZMV, SV, false, true, a);                                               \
     } while (0)
 #define PGR_LAUNCH1(LT, ZMV, SV)                                                                     \
     do {                                                                                             \
@@ -283,7 +310,15 @@ extern "C" int pgr_shoot_fan_device(pgr_env* env, const double* y0, int64_t N, d
         else if (sv == 1) PGR_LAUNCH1(LT, ZMV, 1);                                                   \
         else PGR_LAUNCH1(LT, ZMV, 2);                                                                \
     } while (0)
-    if (flags & PGR_SAMPLE_BLOCKED) {   // (HBM-table path, trajectories, sample-major: checked above)
+    if (log.K && lds_tab) {             // (rows on a linspace grid, default sample form: checked above)
+        if (zm == 1) PGR_LAUNCH_LOG(true, 1, 1); else if (zm == 2) PGR_LAUNCH_LOG(true, 2, 1);
+        else if (zm == 3) PGR_LAUNCH_LOG(true, 3, 1); else if (zm == 4) PGR_LAUNCH_LOG(true, 4, 1); else if (zm == 5) PGR_LAUNCH_LOG(true, 5, 1);
+        else PGR_LAUNCH_LOG(true, 0, 1);
+    } else if (log.K) {                 // (sample-blocked, tables in HBM: checked above)
+        if (zm == 1) PGR_LAUNCH_LOG(false, 1, 3); else if (zm == 2) PGR_LAUNCH_LOG(false, 2, 3);
+        else if (zm == 3) PGR_LAUNCH_LOG(false, 3, 3); else if (zm == 4) PGR_LAUNCH_LOG(false, 4, 3); else if (zm == 5) PGR_LAUNCH_LOG(false, 5, 3);
+        else PGR_LAUNCH_LOG(false, 0, 3);
+    } else if (flags & PGR_SAMPLE_BLOCKED) {   // (HBM-table path, trajectories, sample-major: checked above)
         if (zm == 1) PGR_LAUNCH1(false, 1, 3); else if (zm == 2) PGR_LAUNCH1(false, 2, 3);
         else if (zm == 3) PGR_LAUNCH1(false, 3, 3); else if (zm == 4) PGR_LAUNCH1(false, 4, 3); else if (zm == 5) PGR_LAUNCH1(false, 5, 3);
         else PGR_LAUNCH1(false, 0, 3);
@@ -299,12 +334,33 @@ extern "C" int pgr_shoot_fan_device(pgr_env* env, const double* y0, int64_t N, d
 #undef PGR_LAUNCH
 #undef PGR_LAUNCH1
 #undef PGR_LAUNCH2
+#undef PGR_LAUNCH3
+#undef PGR_LAUNCH_LOG
     const hipError_t launch_err = hipGetLastError();
     // (the placement map is this launch's until its fan kernel has run: `guard` records the slot's event on `st` here
     // and on every error return between the slot's pick and this point)
     guard.release();
     if (launch_err != hipSuccess) return fail(std::string("fan kernel launch: ") + hipGetErrorString(launch_err));
     return 0;
+}
+
+extern "C" int pgr_shoot_fan_device(pgr_env* env, const double* y0, int64_t N, double source_range,
+                                    double receiver_range, const double* r_save, int32_t S,
+                                    double rtol, double atol, uint32_t flags, int64_t max_steps,
+                                    double* T, double* z, double* p, double* end_state,
+                                    int32_t* n_bott, int32_t* n_surf, int32_t* status,
+                                    int32_t* n_steps, int32_t* n_rej, void* stream)
+{
+    return shoot_fan_device(env, y0, N, source_range, receiver_range, r_save, S, rtol, atol, flags, max_steps, T, z, p, end_state,
+                            n_bott, n_surf, status, n_steps, n_rej, stream, FanLog{});
+}
+
+// LOG of the instance the last launch on this environment selected (1: it writes a bounce log), -1 before any launch: the
+// eight slots of pgr_debug_last_instance are all taken
+extern "C" int pgr_debug_last_instance_log(const pgr_env* env)
+{
+    if (!env) return fail("pgr_debug_last_instance_log: null argument");
+    return env->last_instance_log.load(std::memory_order_relaxed);
 }
 
 extern "C" int pgr_debug_last_instance(const pgr_env* env, int32_t out[8])

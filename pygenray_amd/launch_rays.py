@@ -10,7 +10,7 @@ import numpy as np
 from . import _lib
 from .environment import _unpack_envi, _mirror_envi_arrays, _check_monotone
 from .host_physics import bilinear_interp
-from .ray_objects import Ray, RayFan
+from .ray_objects import BounceLog, Ray, RayFan
 
 _DROP_MSG = {
     1: "ray is vertical, terminating integration",
@@ -98,7 +98,7 @@ def _initial_slowness(ode_angles_deg, c):
 
 def _launch_device_fan(source_depth, source_range, ode_angles_deg, receiver_range, num_range_save, environment, rtol,
                        terminate_backwards, flatearth, device=0, max_steps=1_000_000, stored_sign=True,
-                       device_y0=False, spread=1):
+                       device_y0=False, spread=1, max_bounces=None):
     """The fan of _shoot_ode_angles launched device-resident (``_lib.FanHandle``): returns (handle, r) while the kernel
     runs.  ``device_y0``: the initial states are computed on the device from the angles (correctly rounded sine) instead of
     from NumPy's sin(radians(.)) / c on the host (the default, the reference's arithmetic: fans, eigenray trial rays and the
@@ -113,6 +113,8 @@ def _launch_device_fan(source_depth, source_range, ode_angles_deg, receiver_rang
     c = bilinear_interp(x0, source_depth, rin, zin, cin)
     ang = np.asarray(ode_angles_deg, dtype=float).reshape(-1)
     kw = dict(rtol=rtol, terminate_backwards=terminate_backwards, max_steps=max_steps, stored_sign=stored_sign)
+    if max_bounces is not None:
+        kw["max_bounces"] = max_bounces          # (the logged launch, pgr_fan_launch_log)
     if device_y0:
         if spread > 1:
             padded = np.full(len(ang) * int(spread), np.nan)
@@ -139,7 +141,7 @@ def _report_drops(status, debug):
 
 def shoot_rays(source_depth, source_range, launch_angles, receiver_range, num_range_save,
                environment, rtol=1e-9, terminate_backwards=True, n_processes=None, debug=True,
-               flatearth=True, device=0, device_resident=None):
+               flatearth=True, device=0, device_resident=None, max_bounces=None):
     """Integrate a fan of rays (REF/launch_rays.py:11-200) -> ``RayFan``.
 
     ``n_processes`` is accepted for compatibility and ignored (the fan is one GPU launch).
@@ -150,7 +152,18 @@ def shoot_rays(source_depth, source_range, launch_angles, receiver_range, num_ra
     ``device_resident`` (not a reference argument): True -- the call returns when the kernel has finished and the
     per-ray arrays are on the host; the fan's ``ts`` / ``zs`` / ``ps`` stay in HBM and cross PCIe when they are first
     read (``RayFan.from_device``; same values, same shapes); False -- everything is copied before the call returns;
-    None (default) -- device resident from 2 million samples per array on (a 1e5 x 1001 fan: 7 ms instead of 50)."""
+    None (default) -- device resident from 2 million samples per array on (a 1e5 x 1001 fan: 7 ms instead of 50).
+
+    ``max_bounces`` (not a reference argument): None (default) -- exactly the calls above; an int K >= 1 -- the fan keeps a
+    bounce log of K slots per ray (``RayFan.bounces``, ``RayFan.bounce_counts``, ``boundary_loss`` and the ``bottom_loss=`` /
+    ``surface_loss=`` of the amplitude products): the same rays, bit for bit, traced by the kernel
+    instances that also write where each ray bounced.  A surviving ray with more than K bounces raises ``ValueError`` naming
+    the K the fan needs.  With ``device_resident`` False the logged fan is traced device resident and fetched before the call
+    returns."""
+    if max_bounces is not None:
+        if isinstance(max_bounces, bool) or not isinstance(max_bounces, (int, np.integer)) or max_bounces < 1:
+            raise ValueError("max_bounces must be None or an integer >= 1")
+        max_bounces = int(max_bounces)
     if type(launch_angles) is list:
         launch_angles = np.array(launch_angles)
     user = np.asarray(launch_angles, dtype=float)
@@ -162,15 +175,22 @@ def shoot_rays(source_depth, source_range, launch_angles, receiver_range, num_ra
         stored = user            # REF/launch_rays.py:180
     if device_resident is None:
         device_resident = n * int(num_range_save) >= 2_000_000
-    if device_resident and n > 0:
+    if (device_resident or max_bounces is not None) and n > 0:
         h, r = _launch_device_fan(source_depth, source_range, ode, receiver_range, num_range_save, environment, rtol,
-                                  terminate_backwards, flatearth, device=device, stored_sign=True)
+                                  terminate_backwards, flatearth, device=device, stored_sign=True, max_bounces=max_bounces)
         if debug:
             _report_drops(h.status(), debug)
         h.wait()                                    # the kernel; then only the surviving rays' per-ray arrays cross PCIe
         rays = h.fetch_rays_compact(per_ray=stored)
-        return RayFan.from_device(h, rays["per_ray"], r, rays["end"], rays["n_bott"], rays["n_surf"],
-                                  np.full(h.M, source_depth))
+        if max_bounces is not None and h.M:
+            need = int((rays["n_bott"] + rays["n_surf"]).max())
+            if need > max_bounces:
+                h.close()
+                raise ValueError(f"max_bounces={max_bounces} is too small for this fan: a ray bounces {need} times "
+                                 f"(max_bounces={need} holds every bounce)")
+        fan = RayFan.from_device(h, rays["per_ray"], r, rays["end"], rays["n_bott"], rays["n_surf"],
+                                 np.full(h.M, source_depth))
+        return fan if device_resident else fan.to_host()
     # stored convention z -> -z, p -> -p (REF/ray_objects.py:51-52) applied by the kernel's stores
     out = _shoot_ode_angles(source_depth, source_range, ode, receiver_range, num_range_save,
                             environment, rtol, terminate_backwards, flatearth, device=device,
@@ -181,8 +201,11 @@ def shoot_rays(source_depth, source_range, launch_angles, receiver_range, num_ra
     M = int(keep.sum())
     rs = np.tile(out["r"], (M, 1)) if M * S <= 20_000_000 else np.broadcast_to(out["r"], (M, S))
     T, Z, P = out["T"], out["z"], out["p"]  # (M, S) views: dropped rays were squeezed out on the device
-    return RayFan.from_arrays(stored[keep], rs, T, Z, P, out["n_bott"][keep].astype(np.int64),
-                              out["n_surf"][keep].astype(np.int64), np.full(M, source_depth))
+    fan = RayFan.from_arrays(stored[keep], rs, T, Z, P, out["n_bott"][keep].astype(np.int64),
+                             out["n_surf"][keep].astype(np.int64), np.full(M, source_depth))
+    if max_bounces is not None:      # (only a fan of no rays comes this way with a log asked for: its log is empty, not absent)
+        fan._bounces = BounceLog(np.empty((0, max_bounces)), np.empty((0, max_bounces)), np.empty((0, max_bounces), np.int8))
+    return fan
 
 
 def shoot_ray(source_depth, source_range, launch_angle, receiver_range, num_range_save, environment,

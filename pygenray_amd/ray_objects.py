@@ -32,6 +32,73 @@ def _id_strings(numbers, n_botts, n_surfs):
     return np.where((n_botts == 0) & (n_surfs == 0), txt, np.char.add(txt, "b"))
 
 
+class BounceLog:
+    """The bounce log of a fan (``shoot_rays(..., max_bounces=K)``), host arrays over the fan's M rays:
+
+    - ``x`` (M, K): the range of each bounce in the frame the fan was traced in (a backwards fan is traced mirrored: minus
+      the user's range), in the order the bounces happened
+    - ``p`` (M, K): the slowness the ray leaves the bounce with, the stored sign convention of ``RayFan.ps``
+    - ``kind`` (M, K) int8: 0 surface, 1 bottom; -1 in the slots a ray did not use (``x`` and ``p`` are NaN there)
+    - ``count`` (M,) int64: the bounces logged per ray, ``n_botts + n_surfs`` of a fan ``shoot_rays`` returns"""
+
+    def __init__(self, x, p, kind):
+        self.x, self.p, self.kind = np.asarray(x, dtype=float), np.asarray(p, dtype=float), np.asarray(kind, dtype=np.int8)
+
+    @property
+    def count(self):
+        return np.sum(self.kind >= 0, axis=1).astype(np.int64)
+
+    @property
+    def capacity(self):
+        return self.kind.shape[1]
+
+    def __len__(self):
+        return self.kind.shape[0]
+
+    def take(self, idx):
+        return BounceLog(self.x[idx], self.p[idx], self.kind[idx])
+
+    @staticmethod
+    def concatenate(a, b):
+        """two fans' logs, the narrower one padded with empty slots"""
+        K = max(a.capacity, b.capacity)
+
+        def pad(v, fill):
+            out = np.full((v.shape[0], K), fill, dtype=v.dtype)
+            out[:, :v.shape[1]] = v
+            return out
+        return BounceLog(*(np.concatenate([pad(u, f), pad(v, f)]) for u, v, f in
+                           ((a.x, b.x, np.nan), (a.p, b.p, np.nan), (a.kind, b.kind, -1))))
+
+    def sample_index(self, xf):
+        """j_e = argmin_s |xf_s - x_e| (first minimum), the sample from which the reference's _interpolate_ray gives a
+        segment that starts at x_e its samples (REF/launch_rays.py:745-784) -> (M, K) int64; xf: the save ranges in the
+        traced frame.  Slots without an event get len(xf) (beyond every column)."""
+        xf = np.asarray(xf, dtype=float)
+        j = np.zeros(self.x.shape, np.int64)
+        step = max(1, 4_000_000 // max(1, self.x.shape[1] * len(xf)))       # (np.argmin itself, a few million distances at a time)
+        with np.errstate(invalid="ignore"):
+            for m in range(0, self.x.shape[0], step):
+                j[m:m + step] = np.argmin(np.abs(xf[None, None, :] - self.x[m:m + step, :, None]), axis=2)
+        j = np.where(np.isfinite(self.x), j, 0)
+        return np.where(self.kind >= 0, j, len(xf)).astype(np.int64)
+
+    def counts(self, xf, cols):
+        """(n_bott, n_surf), each (M, len(cols)) int64: the logged bounces of each kind that precede the samples at the
+        columns `cols` of the save ranges xf -- the rule of DESIGN.md section 14: an event counts at column s when
+        j_e <= s, and every logged event counts at the last column."""
+        S, cols = len(xf), np.asarray(cols)
+        M, K = self.kind.shape
+        j = self.sample_index(xf)
+        nb, ns = np.zeros((M, len(cols)), np.int64), np.zeros((M, len(cols)), np.int64)
+        step = max(1, 4_000_000 // max(1, K * len(cols)))           # (a few million comparisons at a time, as sample_index)
+        for m in range(0, M, step):
+            hit = (j[m:m + step, :, None] <= cols[None, None, :]) | (cols[None, None, :] == S - 1)
+            for out, kind in ((nb, 1), (ns, 0)):
+                out[m:m + step] = (hit & (self.kind[m:m + step] == kind)[:, :, None]).sum(axis=1)
+        return nb, ns
+
+
 class Ray:
     """Single ray (REF/ray_objects.py:7-59).  ``y`` is ODE-convention [T; z; p] of shape (3, S)."""
 
@@ -80,6 +147,7 @@ class RayFan:
         self.n_surfs = np.asarray(n_surfs)
         self.source_depths = np.asarray(source_depths)
         self._ray_ids = None  # built on first access (a million-ray fan pays 0.2 s for the strings)
+        self._bounces = None
         return self
 
     @classmethod
@@ -99,6 +167,7 @@ class RayFan:
         self.n_surfs = np.asarray(n_surfs)
         self.source_depths = np.asarray(source_depths)
         self._ray_ids = None
+        self._bounces = None     # (a fan launched with a log: fetched from the handle on first access)
         return self
 
     # ts / zs / ps / rs: plain attributes for a host fan, fetched from the device on first access for a device fan
@@ -111,6 +180,7 @@ class RayFan:
                     raise AttributeError(name[1:])
                 d[name] = dev.fetch_samples((key,), compact=True)[key].T     # (M, S) view of the [S][M] block
                 if all(k in d for k in ("_ts", "_zs", "_ps")):
+                    self.bounces            # noqa: B018  (the log, if the fan has one, comes over before the handle goes)
                     dev.close()             # everything is on the host: give the HBM back
                     d["_dev"] = None
             return d[name]
@@ -156,8 +226,46 @@ class RayFan:
         AttributeError); end states, bounce counts and launch angles stay."""
         dev = self.__dict__.get("_dev")
         if dev is not None:
+            self.bounces                    # noqa: B018  (per-ray data, 17 bytes per slot: it stays, like the bounce counts)
             dev.close()
             self.__dict__["_dev"] = None
+
+    # ---- the bounce log (DESIGN.md section 14) ----
+    @property
+    def bounces(self):
+        """The fan's ``BounceLog`` (``shoot_rays(..., max_bounces=K)``), or None for a fan traced without one.  Fetched from
+        the device on first access (K * M * 17 bytes); a device-resident fan stays device resident."""
+        d = self.__dict__
+        if d.get("_bounces") is None:
+            dev = d.get("_dev")
+            if dev is not None and getattr(dev, "K", 0):
+                x, p, k = dev.fetch_bounces()
+                d["_bounces"] = BounceLog(x.T, p.T, k.T)
+        return d.get("_bounces")
+
+    def _has_bounce_log(self):
+        """a log on the host or on the fan's device handle (asking fetches nothing)"""
+        d = self.__dict__
+        return d.get("_bounces") is not None or bool(getattr(d.get("_dev"), "K", 0))
+
+    def _traced_ranges(self):
+        """the save ranges in the frame the fan was traced in (mirrored for a backwards fan)"""
+        r = self.__dict__.get("_r")
+        x = np.asarray(r if r is not None else np.asarray(self.rs)[0], dtype=float)
+        return -x if (len(x) > 1 and x[-1] < x[0]) else x
+
+    def bounce_counts(self, range_indices=None):
+        """The bottom and surface bounces every ray has made on its way to the save columns ``range_indices`` (default
+        ``[S - 1]``; any integers in -S .. S - 1) -> ``(n_bott, n_surf)``, each ``(M, n)`` int64.  A bounce precedes the
+        samples the reference's re-sampling gives the segment that starts at it: column s counts the bounces whose nearest
+        save range (``np.argmin``'s first minimum) is at or before s, and the last column counts them all, so that it
+        equals ``n_botts`` / ``n_surfs``.  Needs a fan traced with a bounce log (``max_bounces=``)."""
+        log = self.bounces
+        if log is None:
+            raise ValueError("the fan has no bounce log: trace it with shoot_rays(..., max_bounces=K)")
+        xf = self._traced_ranges()
+        cols = _columns(range_indices, len(xf))
+        return log.counts(xf, cols)
 
     def __getstate__(self):
         """pickle / copy.deepcopy / multiprocessing: the state of a plain host fan (the reference's RayFan is a plain
@@ -173,6 +281,7 @@ class RayFan:
     def __setstate__(self, state):
         self.__dict__.update(state)
         self.__dict__.setdefault("_ray_ids", None)
+        self.__dict__.setdefault("_bounces", None)
 
     # the state at receiver_range, stored convention, without touching the trajectories
     @property
@@ -272,7 +381,14 @@ class RayFan:
             turns = self.turning_points([k])[:, 0]
             t, z, p = (np.asarray(a)[:, k] for a in (self.ts, self.zs, self.ps))
         rng = np.asarray(self.rs)[:, k] if M else np.zeros(0)
-        return TimeFront(rng, k, self.thetas, t, z, p, turns, self.ray_ids if k == S - 1 else None)
+        if k == S - 1:
+            ids = self.ray_ids
+        elif M and self.bounces is not None:       # a logged fan knows its bounces at every column
+            nb, ns = self.bounce_counts([k])
+            ids = _id_strings(turns * np.sign(self.thetas), nb[:, 0], ns[:, 0])
+        else:
+            ids = None
+        return TimeFront(rng, k, self.thetas, t, z, p, turns, ids)
 
     def __len__(self):
         return len(self.thetas)
@@ -303,9 +419,12 @@ class RayFan:
             idx = idx.reshape(1)
         elif idx.ndim != 1:
             raise ValueError("Invalid indexing array shape")
-        return RayFan.from_arrays(self.thetas[idx], self.rs[idx], self.ts[idx], self.zs[idx],
-                                  self.ps[idx], self.n_botts[idx], self.n_surfs[idx],
-                                  self.source_depths[idx])
+        out = RayFan.from_arrays(self.thetas[idx], self.rs[idx], self.ts[idx], self.zs[idx],
+                                 self.ps[idx], self.n_botts[idx], self.n_surfs[idx],
+                                 self.source_depths[idx])
+        if self.bounces is not None:
+            out._bounces = self.bounces.take(idx)
+        return out
 
     def __add__(self, other):
         """Concatenate along the launch-angle dimension (REF/ray_objects.py:290-345).  Unlike
@@ -316,11 +435,14 @@ class RayFan:
         if not np.array_equal(self.rs[0], other.rs[0]):
             raise ValueError("Range arrays (rs) must be equivalent for concatenation")
         cat = np.concatenate
-        return RayFan.from_arrays(cat([self.thetas, other.thetas]), cat([self.rs, other.rs]),
-                                  cat([self.ts, other.ts]), cat([self.zs, other.zs]),
-                                  cat([self.ps, other.ps]), cat([self.n_botts, other.n_botts]),
-                                  cat([self.n_surfs, other.n_surfs]),
-                                  cat([self.source_depths, other.source_depths]))
+        out = RayFan.from_arrays(cat([self.thetas, other.thetas]), cat([self.rs, other.rs]),
+                                 cat([self.ts, other.ts]), cat([self.zs, other.zs]),
+                                 cat([self.ps, other.ps]), cat([self.n_botts, other.n_botts]),
+                                 cat([self.n_surfs, other.n_surfs]),
+                                 cat([self.source_depths, other.source_depths]))
+        if self.bounces is not None and other.bounces is not None:     # (a sum with an unlogged fan has no log)
+            out._bounces = BounceLog.concatenate(self.bounces, other.bounces)
+        return out
 
     def save_mat(self, filename):
         """.mat export with the reference's schema (REF/ray_objects.py:262-288)."""
@@ -362,9 +484,10 @@ class TimeFront:
     - ``t``, ``z``, ``p``: ``ts[:, k]``, ``zs[:, k]``, ``ps[:, k]``, the stored sign convention, bit for bit
     - ``turning_points`` (int64): the sign changes of p on the way to column k (``RayFan.turning_points``)
     - ``ray_numbers``: ``turning_points * np.sign(thetas)``, the reference's numeric ray id (REF/ray_objects.py:142)
-    - ``ray_ids``: the reference's strings, the number with a ``b`` suffix for a ray that touched a boundary.  The bounce
-      counts ``n_botts`` / ``n_surfs`` are known only at a ray's end, so the strings exist at the fan's last column (where
-      they equal ``RayFan.ray_ids``) and are ``None`` at every other column."""
+    - ``ray_ids``: the reference's strings, the number with a ``b`` suffix for a ray that touched a boundary.  Without a
+      bounce log the counts ``n_botts`` / ``n_surfs`` are known only at a ray's end, so the strings exist at the fan's last
+      column (where they equal ``RayFan.ray_ids``) and are ``None`` at every other column; a fan traced with a bounce log
+      (``shoot_rays(..., max_bounces=K)``) has them at every column, from ``RayFan.bounce_counts``."""
 
     def __init__(self, range, range_index, thetas, t, z, p, turning_points, ray_ids=None):   # noqa: A002
         self.range = range
@@ -506,4 +629,4 @@ class EigenRays:
         io.savemat(filename, {"eigenrays": data})
 
 
-__all__ = ["Ray", "RayFan", "TimeFront", "EigenRays"]
+__all__ = ["Ray", "RayFan", "BounceLog", "TimeFront", "EigenRays"]

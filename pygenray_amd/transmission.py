@@ -54,6 +54,41 @@ def _absorption_profile(absorption):
     return (None if d is None else np.ascontiguousarray(d)), np.ascontiguousarray(a / 1000.0)
 
 
+def _loss_table(loss, name):
+    """A boundary loss as the public functions take it -> (grazing-angle nodes in degrees or None, dB per bounce): None (no
+    loss: 0.0 dB), a scalar in dB per bounce, or a pair ``(grazing_deg, dB)`` of equal-length 1-D sequences, the angles
+    strictly ascending (linear between the nodes, held at the end values outside them).  Everything that can be refused
+    without a GPU is refused here."""
+    if loss is None:
+        return None, np.zeros(1)
+    if isinstance(loss, (tuple, list)) and len(loss) == 2 and np.ndim(loss[0]) == 1:
+        g, v = (np.asarray(a, dtype=float) for a in loss)
+        if v.ndim != 1 or len(v) != len(g) or len(g) == 0:
+            raise ValueError(f"{name} = (grazing_deg, dB) needs two 1-D sequences of equal, non-zero length")
+        if not np.all(np.isfinite(g)) or not np.all(np.diff(g) > 0):
+            raise ValueError(f"{name}: the grazing angles must be finite and strictly ascending")
+    else:
+        g, v = None, np.asarray(loss, dtype=float)
+        if v.ndim != 0:
+            raise ValueError(f"{name} must be a scalar in dB per bounce or a pair (grazing_deg, dB)")
+        v = v.reshape(1)
+    if not np.all(np.isfinite(v)) or np.any(v < 0):
+        raise ValueError(f"{name} must be finite and >= 0 dB")
+    if g is not None and len(g) == 1:
+        g = None
+    return (None if g is None else np.ascontiguousarray(g)), np.ascontiguousarray(v)
+
+
+def _boundary_spec(rays, bottom_loss, surface_loss):
+    """None when neither loss is given (the calls without them), else the two tables; a fan without a bounce log is refused"""
+    if bottom_loss is None and surface_loss is None:
+        return None
+    spec = (_loss_table(bottom_loss, "bottom_loss"), _loss_table(surface_loss, "surface_loss"))
+    if not rays._has_bounce_log():
+        raise ValueError("boundary loss needs a fan traced with a bounce log: shoot_rays(..., max_bounces=K)")
+    return spec
+
+
 class _TracedFan:
     """A fan (host or device resident) on its save ranges x, and -- after ``to_device`` -- the frame it was traced in: xf
     (mirrored for a backwards fan), the EnvHandle and its tables (cin, rin, zin), the torch stream and the fan's device
@@ -104,6 +139,36 @@ class _TracedFan:
                                       a_depths, alpha, out.data_ptr(), self.stream)
         return out
 
+    def bottom_slope(self):
+        """(depth_ranges, bottom_angles in degrees) of the frame the fan was traced in (mirrored for a backwards fan)"""
+        cin, cpin, rin, _, depths, depth_ranges, angles = _unpack_envi(self.environment, flatearth=self.flatearth)
+        if self.backwards:
+            depths, depth_ranges, angles = _mirror_envi_arrays(cin, cpin, rin, depths, depth_ranges, angles)[3:6]
+        return np.ascontiguousarray(depth_ranges, dtype=float), np.ascontiguousarray(angles, dtype=float)
+
+    def boundary_loss(self, spec, counts=False):
+        """The boundary loss B (S, M) in dB every ray has collected up to every save range, a float64 device tensor
+        (csrc/pgr_bounce.h), from the fan's bounce log and the tables `spec` of _boundary_spec; with `counts` also the
+        bottom and surface bounce counts (S, M) int32.  A device-resident fan's log is read where it is; a host fan's is
+        uploaded."""
+        import torch
+        S, M = len(self.x), len(self.rays)
+        out = torch.empty((S, M), dtype=torch.float64, device=self.dev)
+        nb, ns = ((torch.empty((S, M), dtype=torch.int32, device=self.dev) for _ in range(2)) if counts else (None, None))
+        tables = _lib.boundary_tables(spec[0], spec[1], self.bottom_slope())
+        ptr = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
+        if self.handle is not None:
+            self.handle.boundary_loss(tables, out.data_ptr(), ptr(nb), ptr(ns), self.stream)
+        else:
+            log = self.rays.bounces
+            bx, bp = self.upload(log.x.T), self.upload(log.p.T)
+            bk = torch.from_numpy(np.ascontiguousarray(log.kind.T)).to(self.dev)
+            _lib.boundary_loss_device(self.env, bx.data_ptr(), bp.data_ptr(), bk.data_ptr(), M, log.capacity,
+                                      float(self.xf[0]), float(self.xf[-1]), S, tables, out.data_ptr(), ptr(nb), ptr(ns),
+                                      self.stream)
+            torch.cuda.current_stream(self.dev).synchronize()      # (the uploads are freed when this returns)
+        return (out, nb, ns) if counts else out
+
 
 class _FanFrame(_TracedFan):
     """A fan checked for the tube kernels (`who` names the caller in errors): the receiver depths, the save ranges x and the
@@ -137,12 +202,16 @@ class _FanFrame(_TracedFan):
         self.d_W = None
         return self
 
-    def absorb(self, profile):
-        """Volume absorption for the entries ``run`` calls from here on: the path integral of the profile (from
-        _absorption_profile) runs once and becomes, in place, the weights W = 10^(-A / 10) of g, one trajectory array in
-        size, freed with this frame.  None: no weights, the unweighted entries."""
-        if profile is not None:
-            A = self.path_integral(*profile)
+    def absorb(self, profile, boundary=None):
+        """Volume absorption and boundary loss for the entries ``run`` calls from here on: the path integral A of the
+        profile (from _absorption_profile) and the boundary loss B of the tables (from _boundary_spec) run once each and
+        their sum A + B (either alone when the other is None) becomes, in place, the weights W = 10^(-(A + B) / 10) of g, one
+        trajectory array in size, freed with this frame.  Both None: no weights, the unweighted entries."""
+        A = None if profile is None else self.path_integral(*profile)
+        if boundary is not None:
+            B = self.boundary_loss(boundary)
+            A = B if A is None else A.add_(B)
+        if A is not None:
             _lib.absorption_weights_device(self.env.device, A.data_ptr(), A.numel(), A.data_ptr(), self.stream)
             self.d_W = A
         return self
@@ -181,7 +250,8 @@ def _db(out, intensity):
         return -10.0 * np.log10(I)
 
 
-def transmission_loss(rays, receiver_depths, environment, flatearth=True, device=0, intensity=False, absorption=None):
+def transmission_loss(rays, receiver_depths, environment, flatearth=True, device=0, intensity=False, absorption=None,
+                      bottom_loss=None, surface_loss=None):
     """Incoherent ray-tube transmission loss of ``rays`` (a ``RayFan`` from ``shoot_rays``) at ``receiver_depths`` (metres,
     positive down, strictly ascending) on the fan's save ranges -> ndarray ``(len(receiver_depths), S)``:
     ``-10 log10(I)`` dB re 1 m (``+inf`` where no ray tube reaches, NaN in the source's own column), or ``I`` itself with
@@ -200,16 +270,23 @@ def transmission_loss(rays, receiver_depths, environment, flatearth=True, device
     frame's depths as ``receiver_depths``; linear between the nodes, held outside them).  Every ray's g is then weighted by
     10^(-A / 10), A the ray's running loss in dB (``path_loss``), so a tube carries the mean of its two rays' weighted g.
     The weights are one trajectory array on the device for the duration of the call: 0.8 GB for 1e5 rays x 1001 samples,
-    8 GB at 1e6 rays."""
+    8 GB at 1e6 rays.
+
+    ``bottom_loss`` / ``surface_loss`` (default None and None: perfect reflection, exactly the call without them): the loss
+    at every bounce off that boundary, a scalar in dB per bounce or a pair ``(grazing_deg, dB)`` (linear between the
+    nodes, held outside them; the grazing angle is taken against the sloping bottom).  Every ray's g is weighted by
+    10^(-B / 10), B the loss of the bounces that precede the sample (``boundary_loss``); with ``absorption`` the weight is
+    10^(-(A + B) / 10).  Needs a fan traced with a bounce log, ``shoot_rays(..., max_bounces=K)``: ``ValueError`` otherwise."""
     profile = None if absorption is None else _absorption_profile(absorption)
-    f = _FanFrame(rays, receiver_depths, environment, flatearth, "transmission_loss").to_device(device).absorb(profile)
+    boundary = _boundary_spec(rays, bottom_loss, surface_loss)
+    f = _FanFrame(rays, receiver_depths, environment, flatearth, "transmission_loss").to_device(device).absorb(profile, boundary)
     out = f.image()
     f.run("intensity", f.d_depths.data_ptr(), len(f.depths), out.data_ptr())
     return _db(out, intensity)
 
 
 def beam_transmission_loss(rays, receiver_depths, environment, flatearth=True, device=0, intensity=False, min_width=10.0,
-                           absorption=None):
+                           absorption=None, bottom_loss=None, surface_loss=None):
     """Incoherent Gaussian-beam transmission loss of ``rays`` (a ``RayFan`` from ``shoot_rays``) at ``receiver_depths``
     (metres, positive down, strictly ascending) on the fan's save ranges -> ndarray ``(len(receiver_depths), S)``:
     ``-10 log10(I)`` dB re 1 m (``+inf`` where no beam reaches, NaN in the source's own column), or ``I`` itself with
@@ -234,12 +311,15 @@ def beam_transmission_loss(rays, receiver_depths, environment, flatearth=True, d
     device-resident fan is processed where it is and stays device resident.
 
     ``absorption``: volume absorption as in ``transmission_loss`` (E_k takes the weighted g; None, the default, runs
-    exactly the call without it; one trajectory array of device memory for the duration of the call)."""
+    exactly the call without it; one trajectory array of device memory for the duration of the call).
+    ``bottom_loss`` / ``surface_loss``: boundary reflection loss as in ``transmission_loss`` (None and None: exactly the
+    call without them; a fan with a bounce log otherwise)."""
     w = float(min_width)
     if not (np.isfinite(w) and w > 0):
         raise ValueError("min_width must be finite and > 0")
     profile = None if absorption is None else _absorption_profile(absorption)
-    f = _FanFrame(rays, receiver_depths, environment, flatearth, "beam_transmission_loss").to_device(device).absorb(profile)
+    boundary = _boundary_spec(rays, bottom_loss, surface_loss)
+    f = _FanFrame(rays, receiver_depths, environment, flatearth, "beam_transmission_loss").to_device(device).absorb(profile, boundary)
     out, d_b = f.image(), f.upload(f.bottom())
     f.run("beam_intensity", d_b.data_ptr(), f.d_depths.data_ptr(), len(f.depths), w, out.data_ptr())
     return _db(out, intensity)
