@@ -109,13 +109,15 @@ static int fan_launch(pgr_env* env, const double* y0, const double* ode_angles_d
     *out = nullptr;
     if (max_bounces < 0 || (max_bounces > 0 && S < 1)) return fail("pgr_fan_launch_log: need max_bounces >= 1 and trajectories (num_range_save >= 1)");
     if (max_bounces > 0 && (flags & PGR_EXACT_SAMPLES)) return fail("pgr_fan_launch_log: no bounce log with PGR_EXACT_SAMPLES");
+    // what the fan is launched with: sample-major on the linspace grid; environments whose tables stay in HBM / L2: the
+    // sample-blocked kernel, un-blocked when the samples are fetched
+    uint32_t launch_flags = (flags & ~(uint32_t)(PGR_COMPACT | PGR_PACKED_END | PGR_LAUNCH_SLOWNESS | PGR_SAMPLE_BLOCKED)) | PGR_SAMPLE_MAJOR | PGR_SAVE_LINSPACE;
+    const bool blocked = fan_blocked(env, S > 0, launch_flags);
+    if (blocked) launch_flags |= PGR_SAMPLE_BLOCKED;
     if (max_bounces > 0) {
-        // (what pgr_shoot_fan_device would refuse, refused before the upload of y0 is queued)
-        bool lds_tab;
-        int zm;
-        size_t zx_bytes;
-        select_variant(env, lds_tab, zm, zx_bytes);
-        if (!lds_tab && !blocked_layout_fits(env))
+        // (what pgr_shoot_fan_device would refuse -- no LOG instance for this launch --, refused before the upload of y0 is queued)
+        const FanVariant v = select_variant(env);
+        if (!fan_instance_exists(v.lds_tab, v.zm, fan_save(true, launch_flags), false, true))
             return fail("pgr_fan_launch_log: no bounce log for rows on tables in HBM (PGR_OPT_API_BLOCKED off, or no LDS left for the sample-blocked layout)");
     }
     const double t0 = trace_now();
@@ -132,11 +134,8 @@ static int fan_launch(pgr_env* env, const double* y0, const double* ode_angles_d
         std::lock_guard<std::mutex> lock(env->fan_pool_mutex);
         env->live_fans++;
     }
-    f->flags = (flags & ~(uint32_t)(PGR_COMPACT | PGR_PACKED_END | PGR_LAUNCH_SLOWNESS)) | PGR_SAMPLE_MAJOR | PGR_SAVE_LINSPACE;
+    f->flags = launch_flags; f->blocked = blocked;
     f->stream = env->stream;
-    // environments whose tables stay in HBM / L2: the sample-blocked kernel, un-blocked when the samples are fetched
-    f->blocked = fan_blocked(env, f->save, f->flags);
-    if (f->blocked) f->flags |= PGR_SAMPLE_BLOCKED;
     const size_t total = fan_bytes(N, S, f->save, f->blocked);
     {   // the smallest pooled buffer that fits (and is not more than twice too large), else a fresh one
         std::lock_guard<std::mutex> lock(env->fan_pool_mutex);

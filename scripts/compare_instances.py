@@ -1,14 +1,14 @@
 #!/usr/bin/env python3
-"""Compare the gfx950 kernels of two builds of libpgr_hip.so instruction by instruction (DESIGN.md sections 9 and 14: "the
+"""Compare the gfx950 kernels of two builds of libpgr_hip.so instruction by instruction (DESIGN.md sections 9, 14 and 15: "the
 existing instances are unchanged").
 
     python scripts/compare_instances.py OLD/libpgr_hip.so NEW/libpgr_hip.so
 
 The device code object is taken out of each library (objcopy of .hip_fatbin, clang-offload-bundler -unbundle), disassembled
 with llvm-objdump -d, and cut into functions.  Kernels are matched by their demangled name; `pgr_fan_kernel` instances by
-their first four template arguments <LDS_TAB, ZM, SAVE, PERSIST>, so that a template parameter added behind them with a default
-does not unmatch them (instances of the new build whose later arguments are not all false / 0 are new, and are listed as
-such).  The padding behind a kernel is left out.  Per pair: identical, or the instructions that differ -- opcode and operands, addresses and encodings left out --
+their whole template argument list <LDS_TAB, ZM, SAVE, PERSIST, LOG>.  Only when the old build predates a template parameter
+added behind the others with a default (LOG) are its instances matched to those of the new build whose later arguments are
+all false / 0; the new build's other instances are then new, and listed as such.  The padding behind a kernel is left out.  Per pair: identical, or the instructions that differ -- opcode and operands, addresses and encodings left out --
 counted by opcode.  Literals of s_add_u32 / s_addc_u32 after an s_getpc_b64 are PC-relative offsets of constants, which move
 with a kernel's position in the object."""
 import collections
@@ -49,24 +49,34 @@ def functions(lib):
 
 
 def key(name):
+    """-> (key, template arguments or None): `pgr_fan_kernel` instances are keyed by their whole argument list"""
     m = re.match(r".*(pgr_fan_kernel)<([^>]*)>\(", name)
     if not m:
-        return name, True
+        return name, None
     args = [a.strip() for a in m.group(2).split(",")]
-    old = all(a in ("false", "0") for a in args[4:])
-    return m.group(1) + "<" + ", ".join(args[:4]) + ">", old       # (without the signature: the argument struct was renamed)
+    return m.group(1) + "<" + ", ".join(args) + ">", args          # (without the signature: the argument struct was renamed)
+
+
+def keyed(lib):
+    out, n_args = {}, set()
+    for n, body in functions(lib).items():
+        k, args = key(n)
+        out[k] = body
+        if args is not None:
+            n_args.add(len(args))
+    return out, n_args
 
 
 def main(old_lib, new_lib):
-    old = {key(n)[0]: body for n, body in functions(old_lib).items()}
-    new, added = {}, []
-    for n, body in functions(new_lib).items():
-        k, is_old = key(n)
-        if is_old:
-            new[k] = body
-        else:
-            added.append(n)
-    same, differ = 0, 0
+    (old, old_n), (new, new_n) = keyed(old_lib), keyed(new_lib)
+    if old_n and new_n and max(old_n) < max(new_n):
+        # the old build predates a template parameter (LOG): its instances are those of the new build whose later arguments
+        # are all false / 0; the new build's other instances are new
+        pad = lambda k: k[:-1] + ", false" * (max(new_n) - max(old_n)) + ">" if k.startswith("pgr_fan_kernel<") else k  # noqa: E731
+        old = {pad(k): body for k, body in old.items()}
+    count = lambda d: sum(k.startswith("pgr_fan_kernel<") for k in d)  # noqa: E731
+    print(f"pgr_fan_kernel instances: {count(old)} in the old build, {count(new)} in the new build")
+    same, literals, differ = 0, 0, 0
     for k in sorted(old):
         if k not in new:
             print("MISSING in the new build:", k)
@@ -75,15 +85,21 @@ def main(old_lib, new_lib):
         if a == b:
             same += 1
             continue
-        differ += 1
         if len(a) != len(b):
+            differ += 1
             print(f"DIFFERENT LENGTH {len(a)} -> {len(b)}: {k}")
             continue
         ops = collections.Counter(x.split()[0] if x.split()[0] == y.split()[0] else x.split()[0] + "->" + y.split()[0]
                                   for x, y in zip(a, b) if x != y)
+        only_literals = set(ops) <= {"s_add_u32", "s_addc_u32"}
+        literals += only_literals
+        differ += not only_literals
         print(f"{sum(ops.values())} of {len(a)} instructions differ ({dict(ops)}): {k}")
-    print(f"{same} kernels identical, {differ} differ, {len(added)} only in the new build, "
-          f"{len([k for k in new if k not in old])} unmatched old-style kernels in the new build")
+    added = sorted(k for k in new if k not in old)
+    for k in added:
+        print("ONLY in the new build:", k)
+    print(f"{same} kernels identical, {literals} differ in s_add_u32 / s_addc_u32 literals only, {differ} differ otherwise, "
+          f"{len([k for k in old if k not in new])} missing in the new build, {len(added)} only in the new build")
 
 
 if __name__ == "__main__":

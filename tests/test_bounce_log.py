@@ -132,6 +132,48 @@ def test_persistent_logged_instances(lib, which):
     env.close()
 
 
+def test_every_log_instance_is_launched_and_equals_the_unlogged_fan(lib, pr):  # noqa: F811
+    """The 24 LOG instances of pgr_fan_kernel (csrc/pgr_launch.h, fan_instance_exists): <LDS table, SAVE 1> and <HBM tables,
+    SAVE 3> for the six depth look-ups and both PERSIST values.  The environments are those of the instance walk of
+    test_hip_parity.py (its `grids`: depth grid and PGR_OPT_DEPTH_SEARCH per ZM, range-independent / range-dependent
+    tables), the fans its small and its persistent one.  Each launch is confirmed to be the instance it was meant to be, the
+    logged fan is the unlogged fan of the same launch bit for bit, and the log holds n_bott + n_surf slots per ray."""
+    z1 = np.arange(0, 6000, 1.0)
+    depf = pr.eflat(z1, 35.0, pr.munk_ssp(z1))[0]               # the flat-earth image of a uniform grid: smooth, non-uniform
+    grids = {4: (z1, 0), 1: (np.arange(0, 6000, 2.0), 0), 5: (depf, 0), 3: (depf, 3), 2: (depf, 2), 0: (depf, 1)}   # zm -> (zin, PGR_OPT_DEPTH_SEARCH)
+    seen = set()
+    for lds in (1, 0):
+        for zm, (zin, search) in grids.items():
+            r = np.linspace(0.0, 40e3, 7)
+            cin = np.array([munk(zin, 1300.0 + (0.0 if lds else 4e-3 * ri)) for ri in r])
+            arrs = [cin, np.gradient(cin, zin, axis=1, edge_order=1), r, zin, np.full(7, 4800.0), r.copy(), np.zeros(7)]
+            env = lib.EnvHandle(*arrs)
+            env.set_option("depth_search", search)
+            for persist, (n, x1, S, K) in enumerate(((N_SMALL, X_SMALL, S_SMALL, 24), (N_BIG, X_BIG, S_BIG, 6))):
+                want = (lds, zm, 1 if lds else 3, persist)
+                y0 = y0_for(oracle, arrs, 900.0, 0.0, np.linspace(-19.5, 19.5, n))
+                plain = lib.FanHandle(env, 0.0, x1, S, y0=y0)
+                ref = handle_outputs(plain)
+                li = env.last_instance()
+                assert (li["lds_tab"], li["zm"], li["save"], li["persist"], env.last_instance_log()) == want + (0,), (want, li)
+                plain.close()
+                logged = lib.FanHandle(env, 0.0, x1, S, y0=y0, max_bounces=K)
+                got = handle_outputs(logged)
+                li = env.last_instance()
+                assert (li["lds_tab"], li["zm"], li["save"], li["persist"], env.last_instance_log()) == want + (1,), (want, li)
+                seen.add(want + (1,))
+                bk = logged.fetch_bounces()[2]                     # (K, M) over the surviving rays
+                logged.close()
+                total = ref["n_bott"] + ref["n_surf"]
+                assert (total > 0).sum() > 20, want                # (so that nothing below holds vacuously)
+                for k in ref:
+                    assert _same(ref[k], got[k]), (want, k)        # status, counts, n_steps, n_rej, end states, samples
+                ok = ref["status"] == 0
+                assert total[ok].max() <= K and np.array_equal((bk >= 0).sum(axis=0), total[ok]), want
+            env.close()
+    assert len(seen) == 24 and seen == {(lds, zm, 1 if lds else 3, pv, 1) for lds in (1, 0) for zm in range(6) for pv in (0, 1)}
+
+
 def test_capacity_and_refusals(lib, small_cases, pr):  # noqa: F811
     c = small_cases["lds"]
     env, y0 = c["env"], c["y0"]

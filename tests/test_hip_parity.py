@@ -1567,8 +1567,9 @@ def test_persistent_waves_hold_the_same_bits_as_the_static_deal(lib):
 
 
 def test_every_kernel_instance_is_launched_and_bit_identical(lib, capsys):
-    """The library holds 72 instances of pgr_fan_kernel<LDS_TAB, ZM, SAVE, PERSIST> (csrc/pgr_launch.h: select_variant x sv x
-    persistent).  This walks ALL of them: for every (table home, depth look-up) an environment built to select it, for every
+    """The library holds 96 instances of pgr_fan_kernel<LDS_TAB, ZM, SAVE, PERSIST, LOG> (csrc/pgr_launch.h: fan_instance_exists
+    says which), 72 of them without a bounce log.  This walks ALL of those 72 (the 24 LOG instances: tests/test_bounce_log.py,
+    test_every_log_instance_is_launched_and_equals_the_unlogged_fan): for every (table home, depth look-up) an environment built to select it, for every
     SAVE a fan shaped to need it, small fans for the one-packet-per-wave instances and fans of more packets than the chip
     holds waves for the persistent ones -- each launch is confirmed by pgr_debug_last_instance to be the instance it was
     meant to be, and checked against the oracle by rule (A): status, bounce counts, accepted AND rejected steps, end states,
