@@ -6,6 +6,7 @@ is never imported from here).
 """
 import ctypes
 import os
+import re
 import sys
 import subprocess
 
@@ -49,26 +50,54 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-shared", "-mllvm", "-disable-machine-licm",
                "-ffp-contract=off"]
 
-PGR_TERMINATE_BACKWARDS = 1
-PGR_SAMPLE_MAJOR = 2
-PGR_EXACT_BISECTION = 4
-PGR_EXACT_SAMPLES = 32
-PGR_STORED_SIGN = 64
-PGR_COMPACT = 128
-PGR_PACKED_END = 256
-PGR_SAVE_LINSPACE = 8
-PGR_SKIP_NAN_Y0 = 512
-PGR_LAUNCH_SLOWNESS = 1024
-PGR_SAMPLE_BLOCKED = 2048
-
 RAY_STATUS = {0: "ok", 1: "vertical", 2: "bbox", 3: "backward", 4: "step_too_small",
               5: "max_steps", 6: "bottom_angle_range", 7: "event_error", 8: "skipped"}
 
-_dp = ctypes.POINTER(ctypes.c_double)
-_ip = ctypes.POINTER(ctypes.c_int32)
-_i64 = ctypes.c_int64
-_vp = ctypes.c_void_p
+# The C ABI is stated once, in include/pgr.h: its prototypes and PGR_* constants are read from there at import.
+HEADER = os.path.join(_HERE, "..", "include", "pgr.h")
+_BY_VALUE = {"double": ctypes.c_double, "int": ctypes.c_int, "int32_t": ctypes.c_int32, "int64_t": ctypes.c_int64,
+             "uint32_t": ctypes.c_uint32}
+_RETURNS = {"int": ctypes.c_int, "void": None, "const char*": ctypes.c_char_p}
 
+
+def parse_header(text):
+    """The C ABI a header text declares -> (prototypes, constants): prototypes maps every function `pgr_*` to its ctypes
+    (restype, argtypes), constants every `#define PGR_* <integer>[u]` to its value.  The five by-value types of the ABI map
+    to their ctypes; a pointer, an array and a function-pointer typedef of the header are c_void_p (which takes an address,
+    None, a ctypes pointer / array / callback or byref(...) as they are); any other by-value type is an error."""
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    constants = {n: int(v) for n, v in re.findall(r"^[ \t]*#define[ \t]+(PGR_\w+)[ \t]+(\d+)u?[ \t]*$", text, re.M)}
+    text = re.sub(r'^[ \t]*#.*$|extern\s+"C"\s*\{|\}', " ", text, flags=re.M)
+    fn_typedefs = set(re.findall(r"\btypedef\b[^;]*?\(\s*\*\s*(\w+)\s*\)\s*\(", text))
+    prototypes = {}
+    for ret, name, params in re.findall(r"(?:^|;)\s*([\w\s*]+?)\s*\b(pgr_\w+)\s*\(([^()]*)\)\s*(?=;)", text):
+        ret = re.sub(r"\s*\*\s*", "*", " ".join(ret.split()))
+        if ret not in _RETURNS:
+            raise PgrError(f"include/pgr.h: {name} returns {ret!r}, a type the binding does not know")
+        argtypes = []
+        for p in ([] if params.strip() in ("", "void") else params.split(",")):
+            words = [w for w in p.split() if w != "const"]
+            kind = " ".join(words[:-1] if len(words) > 1 else words)   # (the last word is the parameter's name)
+            if "*" in p or "[" in p or kind in fn_typedefs:
+                argtypes.append(ctypes.c_void_p)
+            elif kind in _BY_VALUE:
+                argtypes.append(_BY_VALUE[kind])
+            else:
+                raise PgrError(f"include/pgr.h: {name} takes `{' '.join(p.split())}` by value, a type the binding does "
+                               "not know (add it to _BY_VALUE; it is not bound as a pointer by default)")
+        prototypes[name] = (_RETURNS[ret], argtypes)
+    return prototypes, constants
+
+
+try:
+    with open(HEADER) as _f:
+        PROTOTYPES, _CONSTANTS = parse_header(_f.read())
+except OSError as _e:
+    raise PgrError(f"{HEADER}: the C ABI header cannot be read ({_e}); pygenray_amd binds libpgr_hip.so from it and runs "
+                   "from its source tree") from None
+globals().update(_CONSTANTS)   # PGR_TERMINATE_BACKWARDS, PGR_SAMPLE_MAJOR, ... PGR_OPT_D2H_REGISTER
+
+_REBUILD = "`python -c 'import __graft_entry__ as g; g.build()'`"
 _lib = None
 
 
@@ -204,76 +233,25 @@ def _preload_torch_hip_runtime():
 
 
 def load():
-    """Load libpgr_hip.so; raise loudly if it is absent (no fallback)."""
+    """Load libpgr_hip.so and bind every prototype of include/pgr.h; raise loudly if it is absent (no fallback) or lacks one."""
     global _lib
     if _lib is not None:
         return _lib
     _preload_torch_hip_runtime()
     if not os.path.exists(LIB_PATH):
         raise PgrError(
-            f"{LIB_PATH} not found: the HIP extension is not built. Run "
-            "`python -c 'import __graft_entry__ as g; g.build()'` (needs hipcc"
+            f"{LIB_PATH} not found: the HIP extension is not built. Run {_REBUILD} (needs hipcc"
             + ("; PGR_ARITH=contracted loads the FMA-contracted variant, built by the same call or by "
                "pygenray_amd._lib.build_contracted()" if ARITH == "contracted" else "") +
             "). pygenray_amd has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    L.pgr_last_error.restype = ctypes.c_char_p
-    L.pgr_device_count.restype = ctypes.c_int
-    L.pgr_env_create.restype = ctypes.c_int
-    L.pgr_env_create.argtypes = [ctypes.POINTER(_vp), ctypes.c_int, _dp, _dp, _dp, _dp, _i64, _i64,
-                                 _dp, _dp, _dp, _i64]
-    L.pgr_env_destroy.restype = None
-    L.pgr_env_destroy.argtypes = [_vp]
-    L.pgr_env_query.restype = ctypes.c_int
-    L.pgr_env_query.argtypes = [_vp, ctypes.c_int]
-    fan_common = [_vp, _vp, _i64, ctypes.c_double, ctypes.c_double, _vp, ctypes.c_int32,
-                  ctypes.c_double, ctypes.c_double, ctypes.c_uint32, _i64, _vp, _vp, _vp, _vp, _vp,
-                  _vp, _vp, _vp, _vp]
-    L.pgr_shoot_fan.restype = ctypes.c_int
-    L.pgr_shoot_fan.argtypes = fan_common
-    L.pgr_shoot_fan_device.restype = ctypes.c_int
-    L.pgr_shoot_fan_device.argtypes = fan_common + [_vp]
-    L.pgr_env_set_option.restype = ctypes.c_int
-    L.pgr_env_set_option.argtypes = [_vp, ctypes.c_int, ctypes.c_int, ctypes.c_int]
-    L.pgr_eval_points.restype = ctypes.c_int
-    L.pgr_eval_points.argtypes = [_vp, _dp, _dp, _i64, _dp]
-    # the ray-tube entries (csrc/pgr_tl.h, pgr_arrivals.h, pgr_beams.h): on a fan handle, then on caller buffers
-    i32, f64 = ctypes.c_int32, ctypes.c_double
-    for name, argtypes in (
-            ("pgr_fan_intensity", [_vp, _vp, _vp, _i64, _vp, _vp]),
-            ("pgr_fan_beam_intensity", [_vp, _vp, _vp, _vp, _i64, f64, _vp, _vp]),
-            ("pgr_fan_arrival_counts", [_vp, _vp, _vp, _i64, _vp, i32, _vp, _vp]),
-            ("pgr_fan_arrivals", [_vp, _vp, _vp, _i64, _vp, i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
-            ("pgr_intensity_device", [_vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _i64, _vp, _vp]),
-            ("pgr_beam_intensity_device", [_vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _vp, _i64, f64, _vp, _vp]),
-            ("pgr_arrival_counts_device", [_vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _i64, _vp, i32, _vp, _vp]),
-            ("pgr_arrivals_device", [_vp, _vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _i64, _vp, i32, _vp, _i64] + [_vp] * 6),
-            # the travel-time sensitivity kernel (csrc/pgr_sens.h): a per-ray product, same pair of entries
-            ("pgr_fan_travel_time_kernel", [_vp, _vp, i32, _vp, i32, i32, _vp, _vp]),
-            ("pgr_travel_time_kernel_device", [_vp, _vp, _vp, _i64, i32, _vp, _vp, i32, _vp, i32, i32, _vp, _vp]),
-            # time fronts and turning-point counts (csrc/pgr_front.h)
-            ("pgr_fan_time_front", [_vp, _vp, i32, _vp, _vp, _vp, _vp, _vp]),
-            ("pgr_time_front_device", [ctypes.c_int, _vp, _vp, _vp, _i64, i32, _vp, i32, _vp, _vp, _vp, _vp, _vp]),
-            # path integrals and absorption weights (csrc/pgr_path.h), then the weighted twins of the tube entries
-            ("pgr_fan_path_integral", [_vp, _vp, _vp, i32, _vp, _vp]),
-            ("pgr_path_integral_device", [_vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, i32, _vp, _vp]),
-            ("pgr_absorption_weights_device", [ctypes.c_int, _vp, _i64, _vp, _vp]),
-            ("pgr_fan_intensity_w", [_vp, _vp, _vp, _vp, _i64, _vp, _vp]),
-            ("pgr_fan_beam_intensity_w", [_vp, _vp, _vp, _vp, _vp, _i64, f64, _vp, _vp]),
-            ("pgr_fan_arrivals_w", [_vp, _vp, _vp, _vp, _i64, _vp, i32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
-            ("pgr_intensity_device_w", [_vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _vp, _i64, _vp, _vp]),
-            ("pgr_beam_intensity_device_w", [_vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _vp, _vp, _i64, f64, _vp, _vp]),
-            ("pgr_arrivals_device_w", [_vp, _vp, _vp, _vp, _i64, i32, _vp, _vp, _vp, _vp, _i64, _vp, i32, _vp, _i64] + [_vp] * 6),
-            # the bounce log and boundary reflection loss (csrc/pgr_bounce.h)
-            ("pgr_fan_launch_log", [_vp, _vp, _vp, f64, f64, _i64, f64, f64, i32, f64, f64, ctypes.c_uint32, _i64, i32,
-                                    ctypes.POINTER(_vp)]),
-            ("pgr_fan_fetch_bounces", [_vp, _vp, _vp, _vp]),
-            ("pgr_fan_boundary_loss", [_vp, _vp, _vp, i32, _vp, _vp, i32, _vp, _vp, i32, _vp, _vp, _vp, _vp]),
-            ("pgr_boundary_loss_device", [_vp, _vp, _vp, _vp, _i64, i32, f64, f64, i32, _vp, _vp, i32, _vp, _vp, i32, _vp, _vp, i32,
-                                          _vp, _vp, _vp, _vp]),
-            ("pgr_debug_last_instance_log", [_vp])):
-        getattr(L, name).restype = ctypes.c_int
-        getattr(L, name).argtypes = argtypes
+    for name, (restype, argtypes) in PROTOTYPES.items():
+        try:
+            fn = getattr(L, name)
+        except AttributeError:
+            raise PgrError(f"{LIB_PATH} does not export {name}, which include/pgr.h declares: the library is older than "
+                           f"the header. Rebuild it: {_REBUILD}.") from None
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
 
@@ -287,12 +265,17 @@ def _c(a):
     return np.ascontiguousarray(a, dtype=np.float64)
 
 
-def _p(a):
-    return a.ctypes.data_as(_dp)
+def _addr(a):
+    """The address of a NumPy buffer (None: NULL), as a c_void_p parameter takes it."""
+    return None if a is None else a.ctypes.data
 
 
-def _vptr(a):
-    return None if a is None else ctypes.c_void_p(a.ctypes.data)
+def _twin(name, weights, upto_p0, rest):
+    """Call tube entry `name(*upto_p0, *rest)` or, with `weights` (a device pointer, not 0 / None), its weighted twin
+    `name`_w, whose one more argument follows p0 (include/pgr.h)."""
+    if weights:
+        return check(getattr(load(), name + "_w")(*upto_p0, weights, *rest))
+    check(getattr(load(), name)(*upto_p0, *rest))
 
 
 class EnvHandle:
@@ -306,9 +289,9 @@ class EnvHandle:
             raise ValueError("cin/cpin must have shape (len(rin), len(zin))")
         if not (len(depths) == len(depth_ranges) == len(bottom_angles)):
             raise ValueError("depths, depth_ranges and bottom_angles must have equal length")
-        h = _vp()
-        check(L.pgr_env_create(ctypes.byref(h), int(device), _p(cin), _p(cpin), _p(rin), _p(zin),
-                               len(rin), len(zin), _p(depths), _p(depth_ranges), _p(bottom_angles),
+        h = ctypes.c_void_p()
+        check(L.pgr_env_create(ctypes.byref(h), int(device), _addr(cin), _addr(cpin), _addr(rin), _addr(zin),
+                               len(rin), len(zin), _addr(depths), _addr(depth_ranges), _addr(bottom_angles),
                                len(depths)))
         self._h = h
         self.device = int(device)
@@ -318,8 +301,7 @@ class EnvHandle:
         return load().pgr_env_query(self._h, int(what))
 
     # tuning options of this environment (include/pgr.h; results never depend on them)
-    _OPTIONS = {"waves_per_block": 0, "depth_search": 1, "park": 2, "placement": 3, "persistent": 4, "api_blocked": 5,
-                "d2h_register": 6}
+    _OPTIONS = {n[len("PGR_OPT_"):].lower(): v for n, v in _CONSTANTS.items() if n.startswith("PGR_OPT_")}
 
     def set_option(self, name, a, b=0):
         check(load().pgr_env_set_option(self._h, self._OPTIONS[name], int(a), int(b)))
@@ -377,10 +359,10 @@ class EnvHandle:
         end = np.empty((N, 3))
         nb = np.zeros(N, np.int32); ns = np.zeros(N, np.int32); st = np.zeros(N, np.int32)
         nsteps = np.zeros(N, np.int32); nrej = np.zeros(N, np.int32)
-        check(L.pgr_shoot_fan(self._h, _vptr(y0), N, float(source_range), float(receiver_range),
-                              _vptr(r), S, float(rtol), float(atol), flags, int(max_steps),
-                              _vptr(T), _vptr(Z), _vptr(P), _vptr(end), _vptr(nb), _vptr(ns),
-                              _vptr(st), _vptr(nsteps), _vptr(nrej)))
+        check(L.pgr_shoot_fan(self._h, _addr(y0), N, float(source_range), float(receiver_range),
+                              _addr(r), S, float(rtol), float(atol), flags, int(max_steps),
+                              _addr(T), _addr(Z), _addr(P), _addr(end), _addr(nb), _addr(ns),
+                              _addr(st), _addr(nsteps), _addr(nrej)))
         if save and compact and sample_major:
             # PGR_COMPACT: the trajectories of the M rays with status 0 sit as [S][M] at the start
             # of the buffers
@@ -394,22 +376,15 @@ class EnvHandle:
     def shoot_fan_device(self, y0_ptr, N, source_range, receiver_range, r_ptr, S, rtol, atol, flags,
                          max_steps, T_ptr, Z_ptr, P_ptr, end_ptr, nb_ptr, ns_ptr, st_ptr,
                          nsteps_ptr, nrej_ptr, stream=0):
-        L = load()
-        v = lambda q: ctypes.c_void_p(q) if q else None  # noqa: E731
-        check(L.pgr_shoot_fan_device(self._h, v(y0_ptr), int(N), float(source_range),
-                                     float(receiver_range), v(r_ptr), int(S), float(rtol),
-                                     float(atol), int(flags), int(max_steps), v(T_ptr), v(Z_ptr),
-                                     v(P_ptr), v(end_ptr), v(nb_ptr), v(ns_ptr), v(st_ptr),
-                                     v(nsteps_ptr), v(nrej_ptr), v(stream)))
+        check(load().pgr_shoot_fan_device(self._h, y0_ptr, int(N), float(source_range), float(receiver_range), r_ptr, int(S),
+                                          float(rtol), float(atol), int(flags), int(max_steps), T_ptr, Z_ptr, P_ptr, end_ptr,
+                                          nb_ptr, ns_ptr, st_ptr, nsteps_ptr, nrej_ptr, stream))
 
     def debug_step(self, t, y, h, rtol=1e-9, atol=1e-6):
         """One RK45 step attempt per (t, y, h): y_new[3], f_new[3], error_norm, 0.9 err**-0.2, f[3]."""
         t = _c(t); y = _c(y).reshape(-1, 3); h = _c(h)
         out = np.empty((len(t), 11))
-        L = load()
-        L.pgr_debug_step.restype = ctypes.c_int
-        L.pgr_debug_step.argtypes = [_vp, _dp, _dp, _dp, _i64, ctypes.c_double, ctypes.c_double, _dp]
-        check(L.pgr_debug_step(self._h, _p(t), _p(y), _p(h), len(t), float(rtol), float(atol), _p(out)))
+        check(load().pgr_debug_step(self._h, _addr(t), _addr(y), _addr(h), len(t), float(rtol), float(atol), _addr(out)))
         return out
 
     def eigen_refine(self, th1, th2, z1, z2, receiver_depth, source_depth, source_range, receiver_range, c_source,
@@ -421,18 +396,14 @@ class EnvHandle:
         passes NumPy's, the reference's arithmetic); None: the device's correctly rounded sine.  The callback runs inside
         the search with this environment's workspace lock held: it must not shoot rays or search on THIS EnvHandle
         (include/pgr.h); plain NumPy arithmetic, as the shim's, is what it is for."""
-        L = load()
         th1, th2, z1, z2 = (_c(a).reshape(-1) for a in (th1, th2, z1, z2))
         n = len(th1)
         rd = _c(np.broadcast_to(np.asarray(receiver_depth, dtype=float), (n,)))
         theta = np.full(n, np.nan); zend = np.full(n, np.nan); tend = np.full(n, np.nan)
         state = np.zeros(n, np.int32); ntrial = np.zeros(n, np.int32)
         launches = ctypes.c_int32(0)
-        FN = ctypes.CFUNCTYPE(None, _dp, _i64, _dp, _vp)
-        L.pgr_eigen_refine_depths_fn.restype = ctypes.c_int
-        L.pgr_eigen_refine_depths_fn.argtypes = [_vp, _i64, _vp, _vp, _vp, _vp, _vp] + [ctypes.c_double] * 6 + [
-            ctypes.c_uint32, _i64, ctypes.c_double, ctypes.c_int32, _vp, _vp, _vp, _vp, _vp, ctypes.POINTER(ctypes.c_int32),
-            FN, _vp]
+        dp = ctypes.POINTER(ctypes.c_double)
+        FN = ctypes.CFUNCTYPE(None, dp, ctypes.c_int64, dp, ctypes.c_void_p)   # pgr_slowness_fn
         failure = []
 
         def _cb(ang_p, m, out_p, _user):
@@ -442,23 +413,20 @@ class EnvHandle:
             except BaseException as exc:   # noqa: BLE001
                 failure.append(exc)
                 np.ctypeslib.as_array(out_p, shape=(m,))[:] = np.nan
-        cb = FN(_cb) if slowness is not None else ctypes.cast(None, FN)
-        check(L.pgr_eigen_refine_depths_fn(self._h, n, _vptr(th1), _vptr(th2), _vptr(z1), _vptr(z2), _vptr(rd),
-                                           float(source_depth), float(source_range), float(receiver_range), float(c_source),
-                                           float(rtol), float(atol), PGR_TERMINATE_BACKWARDS if terminate_backwards else 0,
-                                           int(max_steps), float(ztol), int(max_iter), _vptr(theta), _vptr(state), _vptr(ntrial),
-                                           _vptr(zend), _vptr(tend), ctypes.byref(launches), cb, None))
+        cb = FN(_cb) if slowness is not None else None   # (alive until the call has returned)
+        check(load().pgr_eigen_refine_depths_fn(
+            self._h, n, _addr(th1), _addr(th2), _addr(z1), _addr(z2), _addr(rd), float(source_depth), float(source_range),
+            float(receiver_range), float(c_source), float(rtol), float(atol),
+            PGR_TERMINATE_BACKWARDS if terminate_backwards else 0, int(max_steps), float(ztol), int(max_iter), _addr(theta),
+            _addr(state), _addr(ntrial), _addr(zend), _addr(tend), ctypes.byref(launches), cb, None))
         if failure:
             raise failure[0]
         return dict(theta=theta, state=state, n_trial=ntrial, z_end=zend, t_end=tend, launches=int(launches.value))
 
     def last_instance(self):
         """pgr_debug_last_instance: dict(lds_tab, zm, save, persist, blocks, threads, lds_bytes, queue_tail) of the last fan launch."""
-        L = load()
-        L.pgr_debug_last_instance.restype = ctypes.c_int
-        L.pgr_debug_last_instance.argtypes = [_vp, ctypes.POINTER(ctypes.c_int32)]
         out = (ctypes.c_int32 * 8)()
-        check(L.pgr_debug_last_instance(self._h, out))
+        check(load().pgr_debug_last_instance(self._h, out))
         return dict(zip(("lds_tab", "zm", "save", "persist", "blocks", "threads", "lds_bytes", "queue_tail"), (int(v) for v in out)))
 
     def last_instance_log(self):
@@ -469,7 +437,7 @@ class EnvHandle:
     def eval_points(self, x, y):
         x = _c(x); y = _c(y).reshape(-1, 3)
         out = np.empty((len(x), 10))
-        check(load().pgr_eval_points(self._h, _p(x), _p(y), len(x), _p(out)))
+        check(load().pgr_eval_points(self._h, _addr(x), _addr(y), len(x), _addr(out)))
         return out
 
 
@@ -483,17 +451,6 @@ class FanHandle:
         """``max_bounces`` (an int >= 1; None: no log, pgr_fan_launch as ever): pgr_fan_launch_log -- the fan keeps a bounce
         log of that many slots per ray (``fetch_bounces``, ``boundary_loss``)."""
         L = load()
-        L.pgr_fan_launch.restype = ctypes.c_int
-        L.pgr_fan_launch.argtypes = [_vp, _vp, _vp, ctypes.c_double, ctypes.c_double, _i64, ctypes.c_double, ctypes.c_double,
-                                     ctypes.c_int32, ctypes.c_double, ctypes.c_double, ctypes.c_uint32, _i64, ctypes.POINTER(_vp)]
-        L.pgr_fan_wait.restype = ctypes.c_int
-        L.pgr_fan_wait.argtypes = [_vp, ctypes.POINTER(_i64), ctypes.POINTER(_i64)]
-        L.pgr_fan_fetch_rays.restype = ctypes.c_int
-        L.pgr_fan_fetch_rays.argtypes = [_vp] * 7
-        L.pgr_fan_fetch_samples.restype = ctypes.c_int
-        L.pgr_fan_fetch_samples.argtypes = [_vp, _vp, _vp, _vp, ctypes.c_uint32]
-        L.pgr_fan_destroy.restype = None
-        L.pgr_fan_destroy.argtypes = [_vp]
         self._env = env   # keeps the environment (its stream, its tables) alive
         if y0 is not None:
             y0 = _c(y0).reshape(-1, 3)
@@ -508,14 +465,14 @@ class FanHandle:
         flags = (PGR_TERMINATE_BACKWARDS if terminate_backwards else 0) | (PGR_STORED_SIGN if stored_sign else 0) | \
             (PGR_EXACT_SAMPLES if exact_samples else 0) | (PGR_EXACT_BISECTION if exact_bisection else 0) | \
             (PGR_LAUNCH_SLOWNESS if p0 is not None else 0) | (PGR_SKIP_NAN_Y0 if skip_nan else 0)
-        h = _vp()
+        h = ctypes.c_void_p()
         self.K = 0 if max_bounces is None else int(max_bounces)
         if max_bounces is None:
-            check(L.pgr_fan_launch(env._h, _vptr(y0), _vptr(ode_angles_deg), float(source_depth), float(c_source), n,
+            check(L.pgr_fan_launch(env._h, _addr(y0), _addr(ode_angles_deg), float(source_depth), float(c_source), n,
                                    float(x0), float(x1), self.S, float(rtol), float(atol), flags, int(max_steps),
                                    ctypes.byref(h)))
         else:
-            check(L.pgr_fan_launch_log(env._h, _vptr(y0), _vptr(ode_angles_deg), float(source_depth), float(c_source), n,
+            check(L.pgr_fan_launch_log(env._h, _addr(y0), _addr(ode_angles_deg), float(source_depth), float(c_source), n,
                                        float(x0), float(x1), self.S, float(rtol), float(atol), flags, int(max_steps),
                                        self.K, ctypes.byref(h)))
         self._h = h
@@ -528,17 +485,16 @@ class FanHandle:
             self.wait()
         x, p = np.empty((self.K, self.M)), np.empty((self.K, self.M))
         k = np.empty((self.K, self.M), np.int8)
-        check(load().pgr_fan_fetch_bounces(self._h, _vptr(x), _vptr(p), _vptr(k)))
+        check(load().pgr_fan_fetch_bounces(self._h, _addr(x), _addr(p), _addr(k)))
         return x, p, k
 
     def boundary_loss(self, tables, out_ptr, nb_ptr=0, ns_ptr=0, stream=0):
         """pgr_fan_boundary_loss: out[S][M] (device pointer) = the boundary loss in dB of this fan's surviving rays up to
         every save range; `tables` = boundary_tables(...) (host); nb / ns [S][M] int32 device pointers or 0."""
-        check(load().pgr_fan_boundary_loss(self._h, *_table_args(tables), _vp(out_ptr), _vp(nb_ptr or None), _vp(ns_ptr or None),
-                                           _vp(stream or None)))
+        check(load().pgr_fan_boundary_loss(self._h, *_table_args(tables), out_ptr, nb_ptr, ns_ptr, stream))
 
     def wait(self):
-        n, m = _i64(0), _i64(0)
+        n, m = ctypes.c_int64(0), ctypes.c_int64(0)
         check(load().pgr_fan_wait(self._h, ctypes.byref(n), ctypes.byref(m)))
         self.M = int(m.value)
         return int(n.value), self.M
@@ -548,29 +504,26 @@ class FanHandle:
         end = np.empty((n, 3))
         nb = np.empty(n, np.int32); ns = np.empty(n, np.int32); st = np.empty(n, np.int32)
         n1 = np.empty(n, np.int32); n2 = np.empty(n, np.int32)
-        check(load().pgr_fan_fetch_rays(self._h, _vptr(end), _vptr(nb), _vptr(ns), _vptr(st), _vptr(n1), _vptr(n2)))
+        check(load().pgr_fan_fetch_rays(self._h, _addr(end), _addr(nb), _addr(ns), _addr(st), _addr(n1), _addr(n2)))
         self.M = int(np.count_nonzero(st == 0))
         return dict(end=end, n_bott=nb, n_surf=ns, status=st, n_steps=n1, n_rej=n2)
 
     def fetch_rays_compact(self, per_ray=None):
         """The surviving rays only (launch order): end [M, 3], n_bott / n_surf [M] int64 and, squeezed the same way,
         the caller's per-ray array `per_ray` [N] -> [M]."""
-        L = load()
-        L.pgr_fan_fetch_rays_compact.restype = ctypes.c_int
-        L.pgr_fan_fetch_rays_compact.argtypes = [_vp] * 6
         if self.M is None:
             self.wait()
         m = self.M
         end = np.empty((m, 3)); nb = np.empty(m, np.int64); ns = np.empty(m, np.int64)
         src = None if per_ray is None else _c(per_ray).reshape(-1)
         out = None if per_ray is None else np.empty(m)
-        check(L.pgr_fan_fetch_rays_compact(self._h, _vptr(src), _vptr(out), _vptr(end), _vptr(nb), _vptr(ns)))
+        check(load().pgr_fan_fetch_rays_compact(self._h, _addr(src), _addr(out), _addr(end), _addr(nb), _addr(ns)))
         return dict(end=end, n_bott=nb, n_surf=ns, per_ray=out)
 
     def status(self):
         """status [N] (waits for the kernel)."""
         st = np.empty(self.N, np.int32)
-        check(load().pgr_fan_fetch_rays(self._h, None, None, None, _vptr(st), None, None))
+        check(load().pgr_fan_fetch_rays(self._h, None, None, None, _addr(st), None, None))
         self.M = int(np.count_nonzero(st == 0))
         return st
 
@@ -580,7 +533,7 @@ class FanHandle:
             self.wait()
         cols = self.M if compact else self.N
         bufs = {k: (np.empty((self.S, self.N)) if k in which else None) for k in ("T", "z", "p")}
-        check(load().pgr_fan_fetch_samples(self._h, _vptr(bufs["T"]), _vptr(bufs["z"]), _vptr(bufs["p"]),
+        check(load().pgr_fan_fetch_samples(self._h, _addr(bufs["T"]), _addr(bufs["z"]), _addr(bufs["p"]),
                                            PGR_COMPACT if compact else 0))
         return {k: (v.reshape(-1)[:self.S * cols].reshape(self.S, cols) if cols != self.N else v)
                 for k, v in bufs.items() if v is not None}
@@ -590,11 +543,7 @@ class FanHandle:
         rays at the receiver depths (include/pgr.h); p0 holds the M surviving rays' launch slowness.  Enqueued on `stream`.
         `weights` (here and in beam_intensity / arrivals): a device pointer to [S][M] weights of g, which selects the entry's
         weighted twin (pgr_fan_intensity_w); 0: the unweighted entry."""
-        if weights:
-            return check(load().pgr_fan_intensity_w(self._h, _vp(p0_ptr), _vp(weights), _vp(depths_ptr), int(n_depths),
-                                                    _vp(out_ptr), _vp(stream or None)))
-        check(load().pgr_fan_intensity(self._h, _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vp(out_ptr),
-                                       _vp(stream or None)))
+        _twin("pgr_fan_intensity", weights, (self._h, p0_ptr), (depths_ptr, int(n_depths), out_ptr, stream))
 
     def path_integral(self, a_depths, alpha, out_ptr, stream=0):
         """pgr_fan_path_integral: out[S][M] (device pointer) = the running path integral of this fan's surviving rays for
@@ -603,50 +552,41 @@ class FanHandle:
         ad = None if a_depths is None else _c(a_depths).reshape(-1)
         if ad is not None and len(ad) != len(al):
             raise ValueError("a_depths and alpha must have equal length")
-        check(load().pgr_fan_path_integral(self._h, _vptr(ad), _vptr(al), len(al), _vp(out_ptr), _vp(stream or None)))
+        check(load().pgr_fan_path_integral(self._h, _addr(ad), _addr(al), len(al), out_ptr, stream))
 
     def beam_intensity(self, p0_ptr, bottom_ptr, depths_ptr, n_depths, min_width, out_ptr, stream=0, weights=0):
         """pgr_fan_beam_intensity on raw device pointers (ints): out[n_depths][S] = the Gaussian-beam intensity of this fan's
         surviving rays at the receiver depths, bottom[S] the bottom depth at each save range (include/pgr.h)."""
-        if weights:
-            return check(load().pgr_fan_beam_intensity_w(self._h, _vp(p0_ptr), _vp(weights), _vp(bottom_ptr), _vp(depths_ptr),
-                                                         int(n_depths), float(min_width), _vp(out_ptr), _vp(stream or None)))
-        check(load().pgr_fan_beam_intensity(self._h, _vp(p0_ptr), _vp(bottom_ptr), _vp(depths_ptr), int(n_depths),
-                                            float(min_width), _vp(out_ptr), _vp(stream or None)))
+        _twin("pgr_fan_beam_intensity", weights, (self._h, p0_ptr),
+              (bottom_ptr, depths_ptr, int(n_depths), float(min_width), out_ptr, stream))
 
     def arrival_counts(self, p0_ptr, depths_ptr, n_depths, cols, counts_ptr, stream=0):
         """pgr_fan_arrival_counts: counts[n_depths][len(cols)] (int64, device pointer) = the arrivals of this fan's surviving
         rays at each receiver depth and requested column; `cols` is a host sequence of column indices (include/pgr.h)."""
         c = np.ascontiguousarray(cols, dtype=np.int32)
-        check(load().pgr_fan_arrival_counts(self._h, _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vptr(c), len(c),
-                                            _vp(counts_ptr), _vp(stream or None)))
+        check(load().pgr_fan_arrival_counts(self._h, p0_ptr, depths_ptr, int(n_depths), _addr(c), len(c), counts_ptr, stream))
 
     def arrivals(self, p0_ptr, depths_ptr, n_depths, cols, offsets_ptr, n_arrivals, tube_ptr, w_ptr, t_ptr, p_ptr, i_ptr,
                  stream=0, weights=0):
         """pgr_fan_arrivals: the arrivals themselves, written from offsets[j * len(cols) + c] into tube (int32) / w / T / p /
         I (device pointers holding n_arrivals each)."""
         c = np.ascontiguousarray(cols, dtype=np.int32)
-        if weights:
-            return check(load().pgr_fan_arrivals_w(self._h, _vp(p0_ptr), _vp(weights), _vp(depths_ptr), int(n_depths),
-                                                   _vptr(c), len(c), _vp(offsets_ptr), int(n_arrivals), _vp(tube_ptr),
-                                                   _vp(w_ptr), _vp(t_ptr), _vp(p_ptr), _vp(i_ptr), _vp(stream or None)))
-        check(load().pgr_fan_arrivals(self._h, _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vptr(c), len(c),
-                                      _vp(offsets_ptr), int(n_arrivals), _vp(tube_ptr), _vp(w_ptr), _vp(t_ptr), _vp(p_ptr),
-                                      _vp(i_ptr), _vp(stream or None)))
+        _twin("pgr_fan_arrivals", weights, (self._h, p0_ptr),
+              (depths_ptr, int(n_depths), _addr(c), len(c), offsets_ptr, int(n_arrivals), tube_ptr, w_ptr, t_ptr, p_ptr, i_ptr,
+               stream))
 
     def travel_time_kernel(self, ranges_ptr, n_ranges, depths_ptr, n_depths, column, out_ptr, stream=0):
         """pgr_fan_travel_time_kernel on raw device pointers (ints): out[M][n_ranges][n_depths] = the travel-time sensitivity
         kernel of this fan's surviving rays at save column `column` on the grid ranges x depths (include/pgr.h)."""
-        check(load().pgr_fan_travel_time_kernel(self._h, _vp(ranges_ptr), int(n_ranges), _vp(depths_ptr), int(n_depths),
-                                                int(column), _vp(out_ptr), _vp(stream or None)))
+        check(load().pgr_fan_travel_time_kernel(self._h, ranges_ptr, int(n_ranges), depths_ptr, int(n_depths), int(column),
+                                                out_ptr, stream))
 
     def time_front(self, cols, t_ptr, z_ptr, p_ptr, turns_ptr, stream=0):
         """pgr_fan_time_front on raw device pointers (ints; 0 / None: not wanted): t / z / p [len(cols)][M] float64 = the
         surviving rays' samples at the save columns `cols` (a host sequence of column indices), turns [len(cols)][M] int32
         = their turning-point counts up to those columns (include/pgr.h).  Enqueued on `stream`."""
         c = None if cols is None else np.ascontiguousarray(cols, dtype=np.int32)
-        check(load().pgr_fan_time_front(self._h, _vptr(c), 0 if c is None else len(c), _vp(t_ptr or None), _vp(z_ptr or None),
-                                        _vp(p_ptr or None), _vp(turns_ptr or None), _vp(stream or None)))
+        check(load().pgr_fan_time_front(self._h, _addr(c), 0 if c is None else len(c), t_ptr, z_ptr, p_ptr, turns_ptr, stream))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -662,20 +602,13 @@ class FanHandle:
 
 def initial_states_device(device, ang_ptr, n, source_depth, c_source, y0_ptr, stream=0):
     """pgr_initial_states_device on raw device pointers (ints)."""
-    L = load()
-    L.pgr_initial_states_device.restype = ctypes.c_int
-    L.pgr_initial_states_device.argtypes = [ctypes.c_int, _vp, _i64, ctypes.c_double, ctypes.c_double, _vp, _vp]
-    check(L.pgr_initial_states_device(int(device), _vp(ang_ptr), int(n), float(source_depth), float(c_source), _vp(y0_ptr),
-                                      _vp(stream or None)))
+    check(load().pgr_initial_states_device(int(device), ang_ptr, int(n), float(source_depth), float(c_source), y0_ptr, stream))
 
 
 def debug_math(a, b):
     a = _c(a); b = _c(b)
     out = np.empty((len(a), 9))
-    L = load()
-    L.pgr_debug_math.restype = ctypes.c_int
-    L.pgr_debug_math.argtypes = [_dp, _dp, _i64, _dp]
-    check(L.pgr_debug_math(_p(a), _p(b), len(a), _p(out)))
+    check(load().pgr_debug_math(_addr(a), _addr(b), len(a), _addr(out)))
     return out
 
 
@@ -685,9 +618,7 @@ def device_count():
 
 def build_info():
     """pgr_build_info(): layout pass applied or not + arithmetic variant of the loaded library."""
-    L = load()
-    L.pgr_build_info.restype = ctypes.c_char_p
-    return L.pgr_build_info().decode()
+    return load().pgr_build_info().decode()
 
 
 def device_code_sha256(path=None):
@@ -728,13 +659,8 @@ def device_code_sha256(path=None):
 def arrival_histogram_device(device, t_ptr, t_stride, status_ptr, status_stride, n, t_min, t_max, nbins,
                              counts_ptr, stream=0):
     """pgr_arrival_histogram_device on raw device pointers (ints); see include/pgr.h."""
-    L = load()
-    L.pgr_arrival_histogram_device.restype = ctypes.c_int
-    L.pgr_arrival_histogram_device.argtypes = [ctypes.c_int, _vp, _i64, _vp, _i64, _i64, ctypes.c_double,
-                                               ctypes.c_double, ctypes.c_int32, _vp, _vp]
-    check(L.pgr_arrival_histogram_device(int(device), _vp(t_ptr), int(t_stride), _vp(status_ptr or None),
-                                         int(status_stride), int(n), float(t_min), float(t_max), int(nbins),
-                                         _vp(counts_ptr), _vp(stream or None)))
+    check(load().pgr_arrival_histogram_device(int(device), t_ptr, int(t_stride), status_ptr, int(status_stride), int(n),
+                                              float(t_min), float(t_max), int(nbins), counts_ptr, stream))
 
 
 def intensity_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, depths_ptr, n_depths, out_ptr, stream=0,
@@ -743,26 +669,16 @@ def intensity_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, depths
     (stored sign convention) on `env` (an EnvHandle); see include/pgr.h.  `weights` (here and in beam_intensity_device /
     arrivals_device): a device pointer to [n_samples][n_rays] weights of g, which selects the entry's weighted twin
     (pgr_intensity_device_w); 0: the unweighted entry."""
-    if weights:
-        return check(load().pgr_intensity_device_w(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples), _vp(x_ptr),
-                                                   _vp(p0_ptr), _vp(weights), _vp(depths_ptr), int(n_depths), _vp(out_ptr),
-                                                   _vp(stream or None)))
-    check(load().pgr_intensity_device(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples), _vp(x_ptr),
-                                      _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vp(out_ptr), _vp(stream or None)))
+    _twin("pgr_intensity_device", weights, (env._h, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr),
+          (depths_ptr, int(n_depths), out_ptr, stream))
 
 
 def beam_intensity_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, bottom_ptr, depths_ptr, n_depths, min_width,
                           out_ptr, stream=0, weights=0):
     """pgr_beam_intensity_device on raw device pointers (ints): the Gaussian-beam intensity of caller buffers z / p
     [n_samples][n_rays] (stored sign convention) on `env` (an EnvHandle); see include/pgr.h."""
-    if weights:
-        return check(load().pgr_beam_intensity_device_w(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples),
-                                                        _vp(x_ptr), _vp(p0_ptr), _vp(weights), _vp(bottom_ptr),
-                                                        _vp(depths_ptr), int(n_depths), float(min_width), _vp(out_ptr),
-                                                        _vp(stream or None)))
-    check(load().pgr_beam_intensity_device(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples), _vp(x_ptr),
-                                           _vp(p0_ptr), _vp(bottom_ptr), _vp(depths_ptr), int(n_depths), float(min_width),
-                                           _vp(out_ptr), _vp(stream or None)))
+    _twin("pgr_beam_intensity_device", weights, (env._h, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr),
+          (bottom_ptr, depths_ptr, int(n_depths), float(min_width), out_ptr, stream))
 
 
 def arrival_counts_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, depths_ptr, n_depths, cols, counts_ptr,
@@ -770,9 +686,8 @@ def arrival_counts_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, d
     """pgr_arrival_counts_device on raw device pointers (ints) of caller buffers z / p [n_samples][n_rays] (stored sign
     convention) on `env` (an EnvHandle); `cols` a host sequence of column indices; see include/pgr.h."""
     c = np.ascontiguousarray(cols, dtype=np.int32)
-    check(load().pgr_arrival_counts_device(env._h, _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples), _vp(x_ptr),
-                                           _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vptr(c), len(c), _vp(counts_ptr),
-                                           _vp(stream or None)))
+    check(load().pgr_arrival_counts_device(env._h, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr, depths_ptr,
+                                           int(n_depths), _addr(c), len(c), counts_ptr, stream))
 
 
 def arrivals_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, depths_ptr, n_depths, cols, offsets_ptr,
@@ -780,25 +695,17 @@ def arrivals_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, 
     """pgr_arrivals_device on raw device pointers (ints): arrival_counts_device's walk, writing the arrivals; see
     include/pgr.h."""
     c = np.ascontiguousarray(cols, dtype=np.int32)
-    if weights:
-        return check(load().pgr_arrivals_device_w(env._h, _vp(t_ptr), _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples),
-                                                  _vp(x_ptr), _vp(p0_ptr), _vp(weights), _vp(depths_ptr), int(n_depths),
-                                                  _vptr(c), len(c), _vp(offsets_ptr), int(n_arrivals), _vp(tube_ptr),
-                                                  _vp(w_ptr), _vp(t_out_ptr), _vp(p_out_ptr), _vp(i_ptr),
-                                                  _vp(stream or None)))
-    check(load().pgr_arrivals_device(env._h, _vp(t_ptr), _vp(z_ptr), _vp(p_ptr), int(n_rays), int(n_samples),
-                                     _vp(x_ptr), _vp(p0_ptr), _vp(depths_ptr), int(n_depths), _vptr(c), len(c),
-                                     _vp(offsets_ptr), int(n_arrivals), _vp(tube_ptr), _vp(w_ptr), _vp(t_out_ptr),
-                                     _vp(p_out_ptr), _vp(i_ptr), _vp(stream or None)))
+    _twin("pgr_arrivals_device", weights, (env._h, t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr),
+          (depths_ptr, int(n_depths), _addr(c), len(c), offsets_ptr, int(n_arrivals), tube_ptr, w_ptr, t_out_ptr, p_out_ptr,
+           i_ptr, stream))
 
 
 def travel_time_kernel_device(env, t_ptr, z_ptr, n_rays, n_samples, x_ptr, ranges_ptr, n_ranges, depths_ptr, n_depths,
                               column, out_ptr, stream=0):
     """pgr_travel_time_kernel_device on raw device pointers (ints): the travel-time sensitivity kernel of caller buffers
     T / z [n_samples][n_rays] (stored sign convention) on `env` (an EnvHandle); see include/pgr.h."""
-    check(load().pgr_travel_time_kernel_device(env._h, _vp(t_ptr), _vp(z_ptr), int(n_rays), int(n_samples), _vp(x_ptr),
-                                               _vp(ranges_ptr), int(n_ranges), _vp(depths_ptr), int(n_depths), int(column),
-                                               _vp(out_ptr), _vp(stream or None)))
+    check(load().pgr_travel_time_kernel_device(env._h, t_ptr, z_ptr, int(n_rays), int(n_samples), x_ptr, ranges_ptr,
+                                               int(n_ranges), depths_ptr, int(n_depths), int(column), out_ptr, stream))
 
 
 def time_front_device(device, t_ptr, z_ptr, p_ptr, n_rays, n_samples, cols, t_out_ptr, z_out_ptr, p_out_ptr, turns_ptr,
@@ -807,10 +714,8 @@ def time_front_device(device, t_ptr, z_ptr, p_ptr, n_rays, n_samples, cols, t_ou
     host sequence, or None for a NULL list) and the turning-point counts up to them, of caller buffers T / z / p
     [n_samples][n_rays] on `device`; see include/pgr.h."""
     c = None if cols is None else np.ascontiguousarray(cols, dtype=np.int32)
-    check(load().pgr_time_front_device(int(device), _vp(t_ptr or None), _vp(z_ptr or None), _vp(p_ptr or None), int(n_rays),
-                                       int(n_samples), _vptr(c), 0 if c is None else len(c), _vp(t_out_ptr or None),
-                                       _vp(z_out_ptr or None), _vp(p_out_ptr or None), _vp(turns_ptr or None),
-                                       _vp(stream or None)))
+    check(load().pgr_time_front_device(int(device), t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples), _addr(c),
+                                       0 if c is None else len(c), t_out_ptr, z_out_ptr, p_out_ptr, turns_ptr, stream))
 
 
 def path_integral_device(env, t_ptr, z_ptr, n_rays, n_samples, x_ptr, a_depths, alpha, out_ptr, stream=0):
@@ -821,8 +726,8 @@ def path_integral_device(env, t_ptr, z_ptr, n_rays, n_samples, x_ptr, a_depths, 
     ad = None if a_depths is None else _c(a_depths).reshape(-1)
     if ad is not None and len(ad) != len(al):
         raise ValueError("a_depths and alpha must have equal length")
-    check(load().pgr_path_integral_device(env._h, _vp(t_ptr), _vp(z_ptr), int(n_rays), int(n_samples), _vp(x_ptr), _vptr(ad),
-                                          _vptr(al), len(al), _vp(out_ptr), _vp(stream or None)))
+    check(load().pgr_path_integral_device(env._h, t_ptr, z_ptr, int(n_rays), int(n_samples), x_ptr, _addr(ad),
+                                          _addr(al), len(al), out_ptr, stream))
 
 
 def boundary_tables(bottom, surface, beta):
@@ -841,7 +746,7 @@ def boundary_tables(bottom, surface, beta):
 def _table_args(tables):
     args = []
     for x, v in tables:
-        args += [_vptr(x), _vptr(v), len(v)]
+        args += [_addr(x), _addr(v), len(v)]
     return args
 
 
@@ -849,12 +754,11 @@ def boundary_loss_device(env, bx_ptr, bp_ptr, bk_ptr, n_rays, K, x0, x1, n_sampl
                          stream=0):
     """pgr_boundary_loss_device on raw device pointers (ints): the log bx, bp (float64) and bk (int8), [K][n_rays] each, stored
     sign, on the save ranges np.linspace(x0, x1, n_samples) of the frame of `env`."""
-    check(load().pgr_boundary_loss_device(env._h, _vp(bx_ptr), _vp(bp_ptr), _vp(bk_ptr), int(n_rays), int(K), float(x0),
-                                          float(x1), int(n_samples), *_table_args(tables), _vp(out_ptr), _vp(nb_ptr or None),
-                                          _vp(ns_ptr or None), _vp(stream or None)))
+    check(load().pgr_boundary_loss_device(env._h, bx_ptr, bp_ptr, bk_ptr, int(n_rays), int(K), float(x0), float(x1),
+                                          int(n_samples), *_table_args(tables), out_ptr, nb_ptr, ns_ptr, stream))
 
 
 def absorption_weights_device(device, a_ptr, n, w_ptr, stream=0):
     """pgr_absorption_weights_device on raw device pointers (ints): W[i] = 10^(-A[i] / 10) for n path integrals in dB (W may
     be A); see include/pgr.h."""
-    check(load().pgr_absorption_weights_device(int(device), _vp(a_ptr), int(n), _vp(w_ptr), _vp(stream or None)))
+    check(load().pgr_absorption_weights_device(int(device), a_ptr, int(n), w_ptr, stream))

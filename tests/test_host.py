@@ -264,19 +264,108 @@ def test_plots_smoke():
 
 # ---------------------------------------------------------------- the C ABI library
 def test_library_exports_every_declared_symbol():
+    """Every prototype include/pgr.h declares (as the binding parses them) resolves in the built library, and the three
+    longest parameter lists are bound with the arity counted by hand from the header."""
     from pygenray_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "pgr.h")).read()
-    declared = set(re.findall(r"\b(pgr_[a-z_]+)\s*\(", hdr))
-    declared -= {"pgr_shoot_fan_"}
+    declared = set(_lib.PROTOTYPES)
     assert {"pgr_env_create", "pgr_shoot_fan", "pgr_shoot_fan_device", "pgr_last_error"} <= declared
+    assert len(declared) == 50
     path = _lib.build()  # hipcc cross-compiles gfx950 without a GPU
     L = ctypes.CDLL(path)
     for sym in sorted(declared):
         assert hasattr(L, sym), sym
+    for name, arity in (("pgr_shoot_fan_device", 21), ("pgr_arrivals_device_w", 21), ("pgr_boundary_loss_device", 22)):
+        assert len(_lib.PROTOTYPES[name][1]) == arity, name
     # the code object is gfx950 only
     out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", path], capture_output=True, text=True)
     if out.returncode == 0 and "amdgcn" in out.stdout:
         assert "gfx950" in out.stdout
+
+
+def test_header_parser_on_synthetic_texts():
+    """_lib.parse_header: prototypes -> (restype, argtypes) and PGR_* constants, from small header texts."""
+    from pygenray_amd import _lib
+    vp, i32, i64, f64 = ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64, ctypes.c_double
+    protos, consts = _lib.parse_header("""
+        /* int pgr_in_a_comment(int a); */
+        #ifdef __cplusplus
+        extern "C" {
+        #endif
+        #define PGR_H
+        #define PGR_ONE 1u   /* a flag */
+        #define PGR_TWELVE 12
+        typedef struct pgr_env pgr_env;
+        typedef void (*pgr_slowness_fn)(const double* a, int64_t n, double* out, void* user);
+        int pgr_count(void);   // int pgr_in_a_line_comment(void);
+        int pgr_spans(pgr_env** env, int device,
+                      const double* cin,
+                      int64_t nr, uint32_t flags,
+                      double rtol);
+        void pgr_destroy(pgr_env* env);
+        int pgr_array(const pgr_env* env, int32_t out[8]);
+        int pgr_callback(pgr_env* env, int32_t n, pgr_slowness_fn slowness, void* user);
+        const char* pgr_text(void);
+        const char *pgr_text2();
+        #ifdef __cplusplus
+        }
+        #endif
+    """)
+    assert consts == {"PGR_ONE": 1, "PGR_TWELVE": 12}
+    assert protos == {"pgr_count": (ctypes.c_int, []),
+                      "pgr_spans": (ctypes.c_int, [vp, ctypes.c_int, vp, i64, ctypes.c_uint32, f64]),
+                      "pgr_destroy": (None, [vp]),
+                      "pgr_array": (ctypes.c_int, [vp, vp]),
+                      "pgr_callback": (ctypes.c_int, [vp, i32, vp, vp]),
+                      "pgr_text": (ctypes.c_char_p, []),
+                      "pgr_text2": (ctypes.c_char_p, [])}
+    # a by-value type the binding does not know is refused, by name, and never bound as a pointer
+    with pytest.raises(_lib.PgrError, match="pgr_new.*float"):
+        _lib.parse_header("int pgr_ok(int a);\nint pgr_new(pgr_env* env, float x);")
+    with pytest.raises(_lib.PgrError, match="pgr_new.*size_t"):
+        _lib.parse_header("int pgr_new(size_t n);")
+    with pytest.raises(_lib.PgrError, match="pgr_new.*pgr_slowness_fn"):      # (no typedef in this text says what it is)
+        _lib.parse_header("int pgr_new(pgr_slowness_fn f);")
+    with pytest.raises(_lib.PgrError, match="pgr_new.*returns"):
+        _lib.parse_header("double pgr_new(void);")
+
+
+def test_constants_are_the_headers():
+    """The PGR_* attributes of _lib come from include/pgr.h; these are the values, stated independently."""
+    from pygenray_amd import _lib
+    want = dict(PGR_RAY_OK=0, PGR_RAY_VERTICAL=1, PGR_RAY_BBOX=2, PGR_RAY_BACKWARD=3, PGR_RAY_STEP_TOO_SMALL=4,
+                PGR_RAY_MAX_STEPS=5, PGR_RAY_BETA_RANGE=6, PGR_RAY_EVENT_ERROR=7, PGR_RAY_SKIPPED=8,
+                PGR_TERMINATE_BACKWARDS=1, PGR_SAMPLE_MAJOR=2, PGR_EXACT_BISECTION=4, PGR_SAVE_LINSPACE=8, PGR_DEBUG_TRIPS=16,
+                PGR_EXACT_SAMPLES=32, PGR_STORED_SIGN=64, PGR_COMPACT=128, PGR_PACKED_END=256, PGR_SKIP_NAN_Y0=512,
+                PGR_LAUNCH_SLOWNESS=1024, PGR_SAMPLE_BLOCKED=2048,
+                PGR_OPT_WAVES_PER_BLOCK=0, PGR_OPT_DEPTH_SEARCH=1, PGR_OPT_PARK=2, PGR_OPT_PLACEMENT=3, PGR_OPT_PERSISTENT=4,
+                PGR_OPT_API_BLOCKED=5, PGR_OPT_D2H_REGISTER=6)
+    have = {n: getattr(_lib, n) for n in dir(_lib) if n.startswith("PGR_")}
+    assert have == want and all(type(v) is int for v in have.values())
+    assert _lib.EnvHandle._OPTIONS == {"waves_per_block": 0, "depth_search": 1, "park": 2, "placement": 3, "persistent": 4,
+                                       "api_blocked": 5, "d2h_register": 6}
+    assert sorted(_lib.RAY_STATUS) == list(range(9))
+
+
+def test_library_older_than_the_header_is_refused(tmp_path):
+    """A library that lacks a declared symbol is refused by load(), naming the symbol and the rebuild command -- not by an
+    AttributeError at whichever call reaches the missing entry first."""
+    src = tmp_path / "stub.c"
+    src.write_text('const char* pgr_last_error(void) { return ""; }\n')
+    stub = tmp_path / "libstub.so"
+    subprocess.run([os.environ.get("CC", "cc"), "-shared", "-fPIC", "-o", str(stub), str(src)], check=True)
+    code = (
+        "import sys; sys.path.insert(0, %r)\n"
+        "from pygenray_amd import _lib\n"
+        "_lib.LIB_PATH = %r\n"
+        "try:\n"
+        "    _lib.load()\n"
+        "except _lib.PgrError as e:\n"
+        "    print('REFUSED', e)\n"
+    ) % (ROOT, str(stub))
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
+    assert "REFUSED" in out.stdout, out.stderr
+    assert re.search(r"does not export pgr_\w+", out.stdout) and "older than the header" in out.stdout
+    assert "import __graft_entry__ as g; g.build()" in out.stdout
 
 
 def test_no_cpu_fallback_and_oracle_not_imported_by_product(tmp_path):
