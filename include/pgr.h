@@ -563,6 +563,10 @@ int pgr_boundary_loss_device(pgr_env* env, const double* bx, const double* bp, c
                              const double* beta_x, const double* beta_deg, int32_t n_beta, double* out_db, int32_t* nb,
                              int32_t* ns, void* stream);
 
+/* ---- Caustic index and coherent ray-tube pressure: pgr_fan_caustic_index, pgr_caustic_index_device,
+ * pgr_fan_pressure_w, pgr_pressure_device_w.  Part of this ABI, stated in a file of their own beside this one. ---- */
+#include "pgr_coherent.h"
+
 /* What this build of the library is: whether the instruction-layout pass of the build was applied
  * ("relaid: 502 -> 31 straddles ..." or "plain hipcc") and which arithmetic variant was compiled.
  * bench.py puts it into its JSON line so that a measured number names the binary it came from. */

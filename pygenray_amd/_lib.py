@@ -95,6 +95,13 @@ try:
 except OSError as _e:
     raise PgrError(f"{HEADER}: the C ABI header cannot be read ({_e}); pygenray_amd binds libpgr_hip.so from it and runs "
                    "from its source tree") from None
+# ... and the part of it pgr.h includes from a file of its own: the caustic index and the coherent tube sum
+COHERENT_HEADER = os.path.join(_HERE, "..", "include", "pgr_coherent.h")
+try:
+    with open(COHERENT_HEADER) as _f:
+        COHERENT_PROTOTYPES = parse_header(_f.read())[0]
+except OSError as _e:
+    raise PgrError(f"{COHERENT_HEADER}: the C ABI header cannot be read ({_e})") from None
 globals().update(_CONSTANTS)   # PGR_TERMINATE_BACKWARDS, PGR_SAMPLE_MAJOR, ... PGR_OPT_D2H_REGISTER
 
 _REBUILD = "`python -c 'import __graft_entry__ as g; g.build()'`"
@@ -181,7 +188,7 @@ def build(force=False, verbose=False, out=None, extra_flags=()):
     src = os.path.join(CSRC, "pgr_hip.hip")
     hdr = os.path.join(_HERE, "..", "include", "pgr.h")
     # (one translation unit: pgr_hip.hip includes every csrc/*.h -- device building blocks, the fan kernel, the host side in pieces)
-    deps = [src, hdr, os.path.join(_HERE, "_isa_layout.py")] + sorted(
+    deps = [src, hdr, COHERENT_HEADER, os.path.join(_HERE, "_isa_layout.py")] + sorted(
         os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h"))
     if not force and os.path.exists(LIB_PATH):
         if os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(d) for d in deps):
@@ -245,11 +252,11 @@ def load():
                "pygenray_amd._lib.build_contracted()" if ARITH == "contracted" else "") +
             "). pygenray_amd has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in PROTOTYPES.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **COHERENT_PROTOTYPES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError:
-            raise PgrError(f"{LIB_PATH} does not export {name}, which include/pgr.h declares: the library is older than "
+            raise PgrError(f"{LIB_PATH} does not export {name}, which include/pgr.h declares (itself or through pgr_coherent.h): the library is older than "
                            f"the header. Rebuild it: {_REBUILD}.") from None
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -588,6 +595,19 @@ class FanHandle:
         c = None if cols is None else np.ascontiguousarray(cols, dtype=np.int32)
         check(load().pgr_fan_time_front(self._h, _addr(c), 0 if c is None else len(c), t_ptr, z_ptr, p_ptr, turns_ptr, stream))
 
+    def caustic_index(self, nb_ptr, ns_ptr, kappa_ptr, stream=0):
+        """pgr_fan_caustic_index on raw device pointers (ints): kappa[S][M] int32 = the caustics every tube of this fan's
+        surviving rays has passed up to every save range; nb / ns [S][M] int32, the per-sample bounce counts boundary_loss
+        writes, or 0 (a fan without bounces).  Enqueued on `stream`."""
+        check(load().pgr_fan_caustic_index(self._h, nb_ptr, ns_ptr, kappa_ptr, stream))
+
+    def pressure(self, p0_ptr, q_ptr, frequency, depths_ptr, n_depths, re_ptr, im_ptr, stream=0, weights=0):
+        """pgr_fan_pressure_w on raw device pointers (ints): re / im [n_depths][S] = the coherent sum of this fan's ray tubes
+        at the receiver depths; q [S][M] int32 the tubes' phase index in quarter cycles or 0, `weights` as in ``intensity``
+        or 0 (include/pgr.h)."""
+        check(load().pgr_fan_pressure_w(self._h, p0_ptr, weights or None, q_ptr or None, float(frequency), depths_ptr,
+                                        int(n_depths), re_ptr, im_ptr, stream))
+
     def close(self):
         if getattr(self, "_h", None):
             load().pgr_fan_destroy(self._h)
@@ -762,3 +782,19 @@ def absorption_weights_device(device, a_ptr, n, w_ptr, stream=0):
     """pgr_absorption_weights_device on raw device pointers (ints): W[i] = 10^(-A[i] / 10) for n path integrals in dB (W may
     be A); see include/pgr.h."""
     check(load().pgr_absorption_weights_device(int(device), a_ptr, int(n), w_ptr, stream))
+
+
+def caustic_index_device(device, z_ptr, n_rays, n_samples, nb_ptr, ns_ptr, kappa_ptr, stream=0):
+    """pgr_caustic_index_device on raw device pointers (ints; nb / ns 0: absent): kappa[n_samples][n_rays] int32 of caller rows
+    z [n_samples][n_rays] (stored sign convention) on `device`; see include/pgr.h."""
+    check(load().pgr_caustic_index_device(int(device), z_ptr, int(n_rays), int(n_samples), nb_ptr or None, ns_ptr or None,
+                                          kappa_ptr, stream))
+
+
+def pressure_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, q_ptr, frequency, depths_ptr, n_depths, re_ptr,
+                    im_ptr, stream=0, weights=0):
+    """pgr_pressure_device_w on raw device pointers (ints; q / weights 0: absent): the coherent tube sum of caller buffers
+    T / z / p [n_samples][n_rays] (stored sign convention) on `env` (an EnvHandle); see include/pgr.h."""
+    check(load().pgr_pressure_device_w(env._h, t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr,
+                                       weights or None, q_ptr or None, float(frequency), depths_ptr, int(n_depths), re_ptr,
+                                       im_ptr, stream))

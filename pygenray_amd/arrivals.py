@@ -42,6 +42,10 @@ class Arrivals:
       ``launch_angle`` -- the reference's numeric ray id, what tomography matches arrivals to predictions by -- and NaN
       where the two edge rays differ: a tube straddling a turning point has no one identifier.  Both are ``None`` for an
       ``Arrivals`` built without the counts.
+    - lazily: ``caustics`` (int64): the caustics the arrival's tube has passed on its way to the arrival's column,
+      ``caustic_index(rays, environment)[tube, column]`` -- computed on first access from the fan the arrivals were made from,
+      which the ``Arrivals`` of ``arrivals()`` therefore keeps alive (a device-resident fan stays so); ``ValueError`` as
+      ``caustic_index`` raises it (a fan with bounces and no bounce log), and for an ``Arrivals`` built without its fan.
 
     Bounce counts are known only at a ray's end: at the fan's last column, ``rays.n_surfs[tube]`` and
     ``rays.n_botts[tube]`` apply.  The source's own column (r = 0) has no arrivals."""
@@ -61,6 +65,7 @@ class Arrivals:
         self._thetas = thetas
         self._c_rx = c_rx                      # (R, n) sound speed at the receivers, in the traced frame
         self._lazy = {}
+        self._source = None                    # (rays, environment, flatearth, device) of arrivals(): what `caustics` needs
 
     def __len__(self):
         return len(self.tube)
@@ -93,6 +98,19 @@ class Arrivals:
             with np.errstate(invalid="ignore"):
                 self._lazy["received_angle"] = np.degrees(np.arcsin(self.p * self._c_rx[j, c]))
         return self._lazy["received_angle"]
+
+    @property
+    def caustics(self):
+        if "caustics" not in self._lazy:
+            if self._source is None:
+                raise ValueError("these Arrivals were built without their fan: caustics needs arrivals(rays, ...)'s own result")
+            from .coherent import caustic_index
+            rays, environment, flatearth, device = self._source
+            if "_dev" in rays.__dict__ and rays.__dict__["_dev"] is None and "_zs" not in rays.__dict__:
+                raise ValueError("the fan of these Arrivals was released before its depths were read: caustics cannot be computed")
+            kappa = caustic_index(rays, environment, flatearth=flatearth, device=device)
+            self._lazy["caustics"] = kappa[self.tube, self.range_indices[self._pairs()[1]]]
+        return self._lazy["caustics"]
 
     @property
     def ray_number(self):
@@ -135,7 +153,11 @@ def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=N
     one trajectory array of device memory for the duration of the call.
 
     ``bottom_loss`` / ``surface_loss``: boundary reflection loss as in ``transmission_loss``, one more factor of the same
-    weights (None and None, the default: exactly the call without them; a fan with a bounce log otherwise)."""
+    weights (None and None, the default: exactly the call without them; a fan with a bounce log otherwise).
+
+    The ``Arrivals`` returned keeps a reference to ``rays`` and ``environment`` for its lazily computed ``caustics``: a
+    device-resident fan's HBM stays allocated while the ``Arrivals`` lives, unless the fan is fetched (``to_host()``) or
+    ``release()``d -- after a release without its depths read, ``caustics`` raises ``ValueError``."""
     profile = None if absorption is None else _absorption_profile(absorption)
     boundary = _boundary_spec(rays, bottom_loss, surface_loss)
     f = _FanFrame(rays, receiver_depths, environment, flatearth, "arrivals")
@@ -163,9 +185,11 @@ def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=N
     turns = rays.turning_points(cols)
     slot = np.repeat(np.arange(R * n), np.diff(offsets)) % n
     turns = np.stack([turns[tube, slot], turns[tube + 1, slot]], axis=1)
-    return Arrivals(offsets, f.depths, np.asarray(f.x)[cols], cols.astype(np.int64), tube,
-                    w.cpu().numpy(), T.cpu().numpy(), P.cpu().numpy(), I.cpu().numpy(), np.asarray(rays.thetas, dtype=float),
-                    c_rx, turns)
+    out = Arrivals(offsets, f.depths, np.asarray(f.x)[cols], cols.astype(np.int64), tube,
+                   w.cpu().numpy(), T.cpu().numpy(), P.cpu().numpy(), I.cpu().numpy(), np.asarray(rays.thetas, dtype=float),
+                   c_rx, turns)
+    out._source = (rays, environment, flatearth, device)
+    return out
 
 
 __all__ = ["arrivals", "Arrivals"]

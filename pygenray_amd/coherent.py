@@ -1,0 +1,135 @@
+"""Coherent ray-tube field of a fan: ``caustic_index``, ``pressure_field``, ``coherent_transmission_loss`` (DESIGN.md,
+"Coherent ray-tube pressure").
+
+No reference counterpart: pygenray gives back rays, not amplitudes.  The caustic index of every tube and the coherent sum of
+the tubes run in HIP (csrc/pgr_phase.h) on the fan's trajectories where they already are -- in HBM for a device-resident
+fan, uploaded through torch for a host fan.  There is no CPU path.
+"""
+import numpy as np
+
+from . import _lib
+from .transmission import (_FanFrame, _TracedFan, _absorption_profile, _boundary_spec, _check_flatearth, _loss_table, _ptr,
+                           _save_grid)
+
+
+def _needs_counts(rays):
+    """False for a fan none of whose rays bounced; True for a bounced fan whose bounce log holds every bounce; a bounced fan
+    without such a log is refused.  Nothing is fetched or launched."""
+    total = np.asarray(rays.n_botts, dtype=np.int64) + np.asarray(rays.n_surfs, dtype=np.int64)
+    if len(total) == 0 or not total.any():
+        return False
+    if not rays._has_bounce_log():
+        raise ValueError("the fan's rays bounce and it has no bounce log: the caustic index needs the bounces at every save "
+                         "range, trace the fan with shoot_rays(..., max_bounces=K)")
+    log = rays.__dict__.get("_bounces")
+    K = log.capacity if log is not None else rays.__dict__["_dev"].K
+    if int(total.max()) > K:
+        raise ValueError(f"the fan's bounce log overflowed: a ray bounces {int(total.max())} times and the log holds {K} "
+                         f"(max_bounces={int(total.max())} holds every bounce)")
+    return True
+
+
+def _kappa(f, nb, ns):
+    """kappa [S][M] int32 on the device of the traced fan `f` (a _TracedFan after to_device) from the per-sample bounce counts
+    nb, ns [S][M] int32 on that device (None, None: a fan without bounces)"""
+    import torch
+    S, M = len(f.x), len(f.rays)
+    kappa = torch.empty((S, M), dtype=torch.int32, device=f.dev)
+    if f.handle is not None:
+        f.handle.caustic_index(_ptr(nb), _ptr(ns), kappa.data_ptr(), f.stream)
+    else:
+        _lib.caustic_index_device(f.env.device, f._host_fan("zs"), M, S, _ptr(nb), _ptr(ns), kappa.data_ptr(), f.stream)
+    return kappa
+
+
+def caustic_index(rays, env=None, flatearth=True, device=0):
+    """The number of caustics every ray tube of ``rays`` (a ``RayFan`` from ``shoot_rays``) has passed on its way to every
+    save range -> int64 ndarray ``(M - 1, S)``; tube k is rays k and k + 1.  A tube passes a caustic where its signed width
+    d_k+1 - d_k changes sign between two save ranges -- with the mirror flips of reflections undone: the width is taken
+    times (-1)^(bounces), and a sample at which the two rays have bounced a different number of times (the tube is folded
+    over the boundary), or at which either ray has no sample, is passed over.  Column 0 (every ray at the source) never
+    counts.  The save grid must resolve the caustics: two between consecutive save ranges cancel.
+
+    A fan none of whose rays bounced (``n_botts`` and ``n_surfs`` all zero) needs nothing else; a fan with bounces needs
+    its bounce log (``shoot_rays(..., max_bounces=K)``) and ``env`` (with ``flatearth``), the environment it was traced in
+    -- ``ValueError`` naming ``max_bounces`` without a log or with one that overflowed.  A device-resident fan is processed
+    where it is and stays device resident."""
+    if len(rays) < 2:
+        raise ValueError("caustic_index needs a fan of at least 2 rays (one ray tube)")
+    counts = _needs_counts(rays)
+    import torch
+    handle = rays.__dict__.get("_dev")
+    if env is not None:
+        _check_flatearth(env, flatearth)
+        f = _TracedFan(rays, _save_grid(rays), env, flatearth).to_device(device)
+        nb = ns = None
+        if counts:
+            zero = (_loss_table(None, "bottom_loss"), _loss_table(None, "surface_loss"))
+            _, nb, ns = f.boundary_loss(zero, counts=True)
+        kappa = _kappa(f, nb, ns)
+    elif counts:
+        raise ValueError("caustic_index of a fan with bounces needs `env`, the environment the fan was traced in")
+    else:
+        M = len(rays)
+        dev = torch.device("cuda", handle._env.device if handle is not None else int(device))
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if handle is not None:
+            kappa = torch.empty((handle.S, M), dtype=torch.int32, device=dev)
+            handle.caustic_index(0, 0, kappa.data_ptr(), stream)
+        else:
+            z = torch.from_numpy(np.ascontiguousarray(np.asarray(rays.zs, dtype=float).T)).to(dev)
+            kappa = torch.empty(tuple(z.shape), dtype=torch.int32, device=dev)
+            _lib.caustic_index_device(dev.index, z.data_ptr(), M, z.shape[0], 0, 0, kappa.data_ptr(), stream)
+            torch.cuda.current_stream(dev).synchronize()               # (the upload is freed when this returns)
+    return kappa[:, :-1].cpu().numpy().T.astype(np.int64)
+
+
+def pressure_field(rays, receiver_depths, env, frequency, absorption=None, bottom_loss=None, surface_loss=None, flatearth=True,
+                   device=0):
+    """Coherent ray-tube pressure of ``rays`` (a ``RayFan`` from ``shoot_rays``) at ``receiver_depths`` (metres, positive
+    down, strictly ascending) on the fan's save ranges, at ``frequency`` (Hz, finite, >= 0) -> complex128 ndarray
+    ``(len(receiver_depths), S)``, re 1 m: 0 where no ray tube reaches, NaN in the source's own column.  Every tube that
+    ``transmission_loss`` counts at a receiver -- each arrival of ``arrivals`` -- adds
+
+        sqrt(I) exp(i (2 pi f T - (pi / 2) q)),   q = kappa + 2 n_surf
+
+    with the arrival's own intensity I and travel time T (interpolated across the tube), kappa the tube's
+    ``caustic_index`` (-pi/2 per caustic) and n_surf its surface bounces so far (pi each: a pressure-release surface); the
+    bottom is rigid, phase 0.  Summed tube by tube in launch order, so ``abs(p) ** 2`` is ``transmission_loss``'s
+    intensity wherever one tube arrives.  A tube whose two rays have bounced a different number of times (folded over a
+    boundary) is left out: a strip about one tube wide along both boundaries is empty.  The tube spike at a caustic
+    remains.  ``absorption``, ``bottom_loss``, ``surface_loss``: the weights of ``transmission_loss``, exactly (amplitudes
+    take their square root through I).  The frame and the sound speed are ``transmission_loss``'s.  A fan with bounces
+    needs its bounce log (``shoot_rays(..., max_bounces=K)``): ``ValueError`` otherwise.  A device-resident fan is
+    processed where it is and stays device resident."""
+    f0 = float(frequency)
+    if not (np.isfinite(f0) and f0 >= 0):
+        raise ValueError("frequency must be finite and >= 0 Hz")
+    profile = None if absorption is None else _absorption_profile(absorption)
+    boundary = _boundary_spec(rays, bottom_loss, surface_loss)
+    f = _FanFrame(rays, receiver_depths, env, flatearth, "pressure_field")
+    counts = _needs_counts(rays)
+    f.to_device(device).absorb(profile, boundary, counts=counts)      # (one run of the boundary loss: weights and counts)
+    import torch
+    nb, ns = f.d_counts if counts else (None, None)
+    q = _kappa(f, nb, ns)
+    if counts:
+        # on the device: kappa + 2 n_surf where the tube's two rays have bounced alike, -1 (the tube adds nothing) elsewhere
+        same = (nb[:, :-1] == nb[:, 1:]) & (ns[:, :-1] == ns[:, 1:])
+        q[:, :-1] = torch.where(same, q[:, :-1] + 2 * ns[:, :-1], torch.full_like(q[:, :-1], -1))
+    re, im = f.image(), f.image()
+    f.run("pressure", q.data_ptr(), f0, f.d_depths.data_ptr(), len(f.depths), re.data_ptr(), im.data_ptr())
+    return torch.complex(re, im).cpu().numpy()
+
+
+def coherent_transmission_loss(rays, receiver_depths, env, frequency, absorption=None, bottom_loss=None, surface_loss=None,
+                               flatearth=True, device=0):
+    """Coherent ray-tube transmission loss: ``-20 log10 |p|`` dB re 1 m of ``pressure_field``, whose arguments it takes
+    (``+inf`` where no ray tube reaches or the paths cancel, NaN in the source's own column)."""
+    p = pressure_field(rays, receiver_depths, env, frequency, absorption=absorption, bottom_loss=bottom_loss,
+                       surface_loss=surface_loss, flatearth=flatearth, device=device)
+    with np.errstate(divide="ignore"):
+        return -20.0 * np.log10(np.abs(p))
+
+
+__all__ = ["caustic_index", "pressure_field", "coherent_transmission_loss"]

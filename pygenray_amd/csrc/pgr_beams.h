@@ -54,6 +54,8 @@ __device__ __forceinline__ double gexp(double y)
     return ldexp(p, (int)k);
 }
 
+#include "pgr_trig.h"   // gcos2pi, gsin2pi: cos / sin of 2 pi t by a fixed sequence, for the coherent sum (pgr_phase.h)
+
 // the tube walk's arguments (chunks of GB_TUBES tubes; all S columns, no column list) and the beams' own
 struct GbArgs : TlArgs {
     const double* bottom;     // [S] bottom depth at x_s, in the frame the fan was traced in

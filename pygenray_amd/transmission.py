@@ -89,6 +89,11 @@ def _boundary_spec(rays, bottom_loss, surface_loss):
     return spec
 
 
+def _ptr(t):
+    """a device tensor's address, 0 for None"""
+    return 0 if t is None else t.data_ptr()
+
+
 class _TracedFan:
     """A fan (host or device resident) on its save ranges x, and -- after ``to_device`` -- the frame it was traced in: xf
     (mirrored for a backwards fan), the EnvHandle and its tables (cin, rin, zin), the torch stream and the fan's device
@@ -156,7 +161,7 @@ class _TracedFan:
         out = torch.empty((S, M), dtype=torch.float64, device=self.dev)
         nb, ns = ((torch.empty((S, M), dtype=torch.int32, device=self.dev) for _ in range(2)) if counts else (None, None))
         tables = _lib.boundary_tables(spec[0], spec[1], self.bottom_slope())
-        ptr = lambda t: 0 if t is None else t.data_ptr()  # noqa: E731
+        ptr = _ptr
         if self.handle is not None:
             self.handle.boundary_loss(tables, out.data_ptr(), ptr(nb), ptr(ns), self.stream)
         else:
@@ -202,15 +207,22 @@ class _FanFrame(_TracedFan):
         self.d_W = None
         return self
 
-    def absorb(self, profile, boundary=None):
+    def absorb(self, profile, boundary=None, counts=False):
         """Volume absorption and boundary loss for the entries ``run`` calls from here on: the path integral A of the
         profile (from _absorption_profile) and the boundary loss B of the tables (from _boundary_spec) run once each and
         their sum A + B (either alone when the other is None) becomes, in place, the weights W = 10^(-(A + B) / 10) of g, one
-        trajectory array in size, freed with this frame.  Both None: no weights, the unweighted entries."""
+        trajectory array in size, freed with this frame.  Both None: no weights, the unweighted entries.  `counts`: the same
+        run of the boundary loss (with zero-loss tables when `boundary` is None, its B then unused) also leaves the
+        per-sample bounce counts nb, ns (S, M) int32 in ``self.d_counts``."""
         A = None if profile is None else self.path_integral(*profile)
-        if boundary is not None:
-            B = self.boundary_loss(boundary)
-            A = B if A is None else A.add_(B)
+        self.d_counts = None
+        if boundary is not None or counts:
+            spec = boundary if boundary is not None else (_loss_table(None, "bottom_loss"), _loss_table(None, "surface_loss"))
+            B = self.boundary_loss(spec, counts=counts)
+            if counts:
+                B, *self.d_counts = B
+            if boundary is not None:
+                A = B if A is None else A.add_(B)
         if A is not None:
             _lib.absorption_weights_device(self.env.device, A.data_ptr(), A.numel(), A.data_ptr(), self.stream)
             self.d_W = A
@@ -218,13 +230,14 @@ class _FanFrame(_TracedFan):
 
     def run(self, entry, *args):
         """Tube entry `entry` on the fan, with p0, the arguments after it and the stream: ``FanHandle.<entry>`` on a
-        device-resident fan, else ``_lib.<entry>_device`` on the host fan's trajectories (ts only for ``arrivals``)."""
+        device-resident fan, else ``_lib.<entry>_device`` on the host fan's trajectories (ts only for ``arrivals`` and
+        ``pressure``)."""
         args = (self.d_p0.data_ptr(),) + args + (self.stream,)
         # (the arrival counts have no weighted twin: finite weights leave the tubes counted as they are)
         kw = {"weights": self.d_W.data_ptr()} if self.d_W is not None and entry != "arrival_counts" else {}
         if self.handle is not None:
             return getattr(self.handle, entry)(*args, **kw)
-        fan = [self._host_fan(k) for k in (("ts", "zs", "ps") if entry == "arrivals" else ("zs", "ps"))]
+        fan = [self._host_fan(k) for k in (("ts", "zs", "ps") if entry in ("arrivals", "pressure") else ("zs", "ps"))]
         getattr(_lib, entry + "_device")(self.env, *fan, len(self.rays), len(self.x), self._host_fan("xf"), *args, **kw)
 
     def image(self):
