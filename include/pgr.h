@@ -567,6 +567,10 @@ int pgr_boundary_loss_device(pgr_env* env, const double* bx, const double* bp, c
  * pgr_fan_pressure_w, pgr_pressure_device_w.  Part of this ABI, stated in a file of their own beside this one. ---- */
 #include "pgr_coherent.h"
 
+/* ---- Received time series of a Gaussian pulse from ray-tube arrivals: pgr_signal_device.  Part of
+ * this ABI, stated in a file of its own beside this one. ---- */
+#include "pgr_signal.h"
+
 /* What this build of the library is: whether the instruction-layout pass of the build was applied
  * ("relaid: 502 -> 31 straddles ..." or "plain hipcc") and which arithmetic variant was compiled.
  * bench.py puts it into its JSON line so that a measured number names the binary it came from. */

@@ -102,6 +102,13 @@ try:
         COHERENT_PROTOTYPES = parse_header(_f.read())[0]
 except OSError as _e:
     raise PgrError(f"{COHERENT_HEADER}: the C ABI header cannot be read ({_e})") from None
+# ... and the received signal of a Gaussian pulse, likewise
+SIGNAL_HEADER = os.path.join(_HERE, "..", "include", "pgr_signal.h")
+try:
+    with open(SIGNAL_HEADER) as _f:
+        SIGNAL_PROTOTYPES = parse_header(_f.read())[0]
+except OSError as _e:
+    raise PgrError(f"{SIGNAL_HEADER}: the C ABI header cannot be read ({_e})") from None
 globals().update(_CONSTANTS)   # PGR_TERMINATE_BACKWARDS, PGR_SAMPLE_MAJOR, ... PGR_OPT_D2H_REGISTER
 
 _REBUILD = "`python -c 'import __graft_entry__ as g; g.build()'`"
@@ -188,7 +195,7 @@ def build(force=False, verbose=False, out=None, extra_flags=()):
     src = os.path.join(CSRC, "pgr_hip.hip")
     hdr = os.path.join(_HERE, "..", "include", "pgr.h")
     # (one translation unit: pgr_hip.hip includes every csrc/*.h -- device building blocks, the fan kernel, the host side in pieces)
-    deps = [src, hdr, COHERENT_HEADER, os.path.join(_HERE, "_isa_layout.py")] + sorted(
+    deps = [src, hdr, COHERENT_HEADER, SIGNAL_HEADER, os.path.join(_HERE, "_isa_layout.py")] + sorted(
         os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h"))
     if not force and os.path.exists(LIB_PATH):
         if os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(d) for d in deps):
@@ -252,11 +259,11 @@ def load():
                "pygenray_amd._lib.build_contracted()" if ARITH == "contracted" else "") +
             "). pygenray_amd has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**PROTOTYPES, **COHERENT_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **COHERENT_PROTOTYPES, **SIGNAL_PROTOTYPES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError:
-            raise PgrError(f"{LIB_PATH} does not export {name}, which include/pgr.h declares (itself or through pgr_coherent.h): the library is older than "
+            raise PgrError(f"{LIB_PATH} does not export {name}, which include/pgr.h declares (itself or through pgr_coherent.h / pgr_signal.h): the library is older than "
                            f"the header. Rebuild it: {_REBUILD}.") from None
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -798,3 +805,12 @@ def pressure_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, 
     check(load().pgr_pressure_device_w(env._h, t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr,
                                        weights or None, q_ptr or None, float(frequency), depths_ptr, int(n_depths), re_ptr,
                                        im_ptr, stream))
+
+
+def signal_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, tstart_ptr, frequency, inv_sigma, dt, n_times, re_ptr,
+                  im_ptr, stream=0):
+    """pgr_signal_device on raw device pointers (ints; q 0: absent): re / im [n_groups][n_times] = the complex baseband signal
+    of a Gaussian pulse (inv_sigma = 1 / sigma; 0: CW) summed over the arrivals T / I / q of each group [offsets[g],
+    offsets[g + 1]) at the times tstart[g] + n dt; see include/pgr_signal.h."""
+    check(load().pgr_signal_device(int(device), offsets_ptr, int(n_groups), t_ptr, i_ptr, q_ptr or None, tstart_ptr,
+                                   float(frequency), float(inv_sigma), float(dt), int(n_times), re_ptr, im_ptr, stream))

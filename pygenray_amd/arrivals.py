@@ -136,6 +136,25 @@ class Arrivals:
                 f"{len(self.range_indices)} ranges)")
 
 
+def _device_arrivals(f, cols):
+    """The arrivals of the frame `f` (a _FanFrame after to_device and absorb) at its receiver depths and the save columns
+    `cols`, left on the device -> (offsets int64 [R * n + 1], tube int32, w, T, p, I float64 [n_arrivals]): the count, the scan
+    and the emit entries, in ``Arrivals``' order."""
+    import torch
+    R, n = len(f.depths), len(cols)
+    counts = torch.empty(R * n, dtype=torch.int64, device=f.dev)
+    f.run("arrival_counts", f.d_depths.data_ptr(), R, cols, counts.data_ptr())
+    offsets = torch.zeros(R * n + 1, dtype=torch.int64, device=f.dev)
+    torch.cumsum(counts, 0, out=offsets[1:])
+    total = int(offsets[-1].item())
+    tube = torch.empty(total, dtype=torch.int32, device=f.dev)
+    w, T, P, I = (torch.empty(total, dtype=torch.float64, device=f.dev) for _ in range(4))
+    if total:
+        f.run("arrivals", f.d_depths.data_ptr(), R, cols, offsets.data_ptr(), total, tube.data_ptr(), w.data_ptr(),
+              T.data_ptr(), P.data_ptr(), I.data_ptr())
+    return offsets, tube, w, T, P, I
+
+
 def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=None, device=0, absorption=None,
              bottom_loss=None, surface_loss=None):
     """Ray-tube arrivals of ``rays`` (a ``RayFan`` from ``shoot_rays``) at ``receiver_depths`` (metres, positive down,
@@ -164,19 +183,8 @@ def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=N
     S = len(f.x)
     cols = _columns(range_indices, S)
     f.to_device(device).absorb(profile, boundary)
-    import torch
-
     R, n = len(f.depths), len(cols)
-    counts = torch.empty(R * n, dtype=torch.int64, device=f.dev)
-    f.run("arrival_counts", f.d_depths.data_ptr(), R, cols, counts.data_ptr())
-    offsets = torch.zeros(R * n + 1, dtype=torch.int64, device=f.dev)
-    torch.cumsum(counts, 0, out=offsets[1:])
-    total = int(offsets[-1].item())
-    tube = torch.empty(total, dtype=torch.int32, device=f.dev)
-    w, T, P, I = (torch.empty(total, dtype=torch.float64, device=f.dev) for _ in range(4))
-    if total:
-        f.run("arrivals", f.d_depths.data_ptr(), R, cols, offsets.data_ptr(), total, tube.data_ptr(), w.data_ptr(),
-              T.data_ptr(), P.data_ptr(), I.data_ptr())
+    offsets, tube, w, T, P, I = _device_arrivals(f, cols)
     cin, rin, zin = f.tables
     xs = f.xf[cols]
     c_rx = _bilinear(np.broadcast_to(xs[None, :], (R, n)), np.broadcast_to(f.depths[:, None], (R, n)), rin, zin, cin)

@@ -42,6 +42,20 @@ def _kappa(f, nb, ns):
     return kappa
 
 
+def _phase_index(f, counts):
+    """q [S][M] int32 on the device of the frame `f` (a _FanFrame after to_device and absorb(..., counts=counts)): the tubes'
+    phase index in quarter cycles, kappa + 2 n_surf where the tube's two rays have bounced alike and -1 (the tube adds
+    nothing) elsewhere; kappa itself for a fan without bounces (`counts` False)."""
+    import torch
+    nb, ns = f.d_counts if counts else (None, None)
+    q = _kappa(f, nb, ns)
+    if counts:
+        # on the device: kappa + 2 n_surf where the tube's two rays have bounced alike, -1 (the tube adds nothing) elsewhere
+        same = (nb[:, :-1] == nb[:, 1:]) & (ns[:, :-1] == ns[:, 1:])
+        q[:, :-1] = torch.where(same, q[:, :-1] + 2 * ns[:, :-1], torch.full_like(q[:, :-1], -1))
+    return q
+
+
 def caustic_index(rays, env=None, flatearth=True, device=0):
     """The number of caustics every ray tube of ``rays`` (a ``RayFan`` from ``shoot_rays``) has passed on its way to every
     save range -> int64 ndarray ``(M - 1, S)``; tube k is rays k and k + 1.  A tube passes a caustic where its signed width
@@ -111,12 +125,7 @@ def pressure_field(rays, receiver_depths, env, frequency, absorption=None, botto
     counts = _needs_counts(rays)
     f.to_device(device).absorb(profile, boundary, counts=counts)      # (one run of the boundary loss: weights and counts)
     import torch
-    nb, ns = f.d_counts if counts else (None, None)
-    q = _kappa(f, nb, ns)
-    if counts:
-        # on the device: kappa + 2 n_surf where the tube's two rays have bounced alike, -1 (the tube adds nothing) elsewhere
-        same = (nb[:, :-1] == nb[:, 1:]) & (ns[:, :-1] == ns[:, 1:])
-        q[:, :-1] = torch.where(same, q[:, :-1] + 2 * ns[:, :-1], torch.full_like(q[:, :-1], -1))
+    q = _phase_index(f, counts)
     re, im = f.image(), f.image()
     f.run("pressure", q.data_ptr(), f0, f.d_depths.data_ptr(), len(f.depths), re.data_ptr(), im.data_ptr())
     return torch.complex(re, im).cpu().numpy()

@@ -1,0 +1,116 @@
+"""``received_signal``: the time series a receiver records when the source sends a Gaussian pulse, summed over the fan's
+ray-tube arrivals ("Received signal of a Gaussian pulse").
+
+No reference counterpart: pygenray gives back rays, not amplitudes.  The arrivals (csrc/pgr_arrivals.h), their phase index
+(csrc/pgr_phase.h) and the sum over them at every time sample (csrc/pgr_signal.h) run in HIP and stay on the device from the
+fan to the signal -- in HBM for a device-resident fan, uploaded through torch for a host fan.  There is no CPU path.
+"""
+import math
+
+import numpy as np
+
+from . import _lib
+from .arrivals import _device_arrivals
+from .coherent import _needs_counts, _phase_index
+from .ray_objects import _columns
+from .transmission import _FanFrame, _absorption_profile, _boundary_spec
+
+
+def pulse_sigma(bandwidth):
+    """The width sigma (seconds) of the Gaussian envelope exp(-t^2 / (2 sigma^2)) whose spectrum has the half-power full
+    bandwidth ``bandwidth`` (Hz, finite, >= 0): sigma = sqrt(ln 2) / (pi B); ``inf`` for 0, a continuous wave."""
+    B = float(bandwidth)
+    if not (math.isfinite(B) and B >= 0):
+        raise ValueError("bandwidth must be finite and >= 0 Hz")
+    return math.inf if B == 0 else math.sqrt(math.log(2.0)) / (math.pi * B)
+
+
+def _inv_sigma(bandwidth):
+    """1 / sigma of ``pulse_sigma``, formed without the detour over inf: pi B / sqrt(ln 2), 0.0 for B = 0"""
+    B = float(bandwidth)
+    if not (math.isfinite(B) and B >= 0):
+        raise ValueError("bandwidth must be finite and >= 0 Hz")
+    return math.pi * B / math.sqrt(math.log(2.0))
+
+
+def received_signal(rays, receiver_depths, env, frequency, bandwidth, t0, dt, n_times, range_indices=None, absorption=None,
+                    bottom_loss=None, surface_loss=None, flatearth=True, device=0):
+    """The complex-demodulated signal of ``rays`` (a ``RayFan`` from ``shoot_rays``) at ``receiver_depths`` (metres, positive
+    down, strictly ascending) and the save columns ``range_indices`` (default ``[S - 1]``, as in ``arrivals``) when the source
+    sends a Gaussian pulse of centre ``frequency`` (Hz, finite, >= 0) and half-power full bandwidth ``bandwidth`` (Hz,
+    finite, >= 0) -> complex128 ndarray ``(R, n, n_times)``, re 1 m, at the times ``t0 + arange(n_times) * dt`` (``dt`` > 0
+    seconds; ``t0`` a scalar or one value per requested column, e.g. the reduced time x / c_red).  Every arrival of
+    ``arrivals`` -- every tube ``pressure_field`` adds -- contributes
+
+        u(t) += sqrt(I) exp(i (2 pi f T - (pi / 2) q)) E(t - T),   E(tau) = exp(-tau^2 / (2 sigma^2)),  q = kappa + 2 n_surf
+
+    with sigma = ``pulse_sigma(bandwidth)``, the envelope cut at 8 sigma (E = 1.3e-14), summed arrival by arrival in tube
+    order.  u is the baseband signal; the analytic passband signal is ``u(t) exp(-2j pi f t)``, in ``pressure_field``'s sign
+    convention.  ``bandwidth=0`` is the CW limit: every sample equals ``pressure_field(...)[j, column]``.  A requested column
+    with r = 0 is NaN, as in ``pressure_field``; where no arrival is within 8 sigma the signal is 0.
+
+    ``absorption``, ``bottom_loss``, ``surface_loss``: the weights of ``transmission_loss``, exactly.  The absorption
+    weights are those of the one profile given, i.e. of the centre frequency: they are not varied across the band.  The
+    frame, the sound speed and the errors are ``pressure_field``'s (a fan with bounces needs its bounce log,
+    ``shoot_rays(..., max_bounces=K)``).  ``ValueError`` when ``R * n * n_times`` complex samples do not fit in the free
+    device memory, before any kernel runs.  A device-resident fan is processed where it is and stays device resident."""
+    f0 = float(frequency)
+    if not (np.isfinite(f0) and f0 >= 0):
+        raise ValueError("frequency must be finite and >= 0 Hz")
+    rs = _inv_sigma(bandwidth)
+    step = float(dt)
+    if not (np.isfinite(step) and step > 0):
+        raise ValueError("dt must be finite and > 0 seconds")
+    if isinstance(n_times, (bool, float)) or int(n_times) != n_times or int(n_times) < 1:
+        raise ValueError("n_times must be an integer >= 1")
+    nt = int(n_times)
+    if nt > 65535 * 256:
+        raise ValueError(f"n_times must be <= {65535 * 256}")
+    profile = None if absorption is None else _absorption_profile(absorption)
+    boundary = _boundary_spec(rays, bottom_loss, surface_loss)
+    f = _FanFrame(rays, receiver_depths, env, flatearth, "received_signal")
+    counts = _needs_counts(rays)
+    cols = _columns(range_indices, len(f.x))
+    R, n = len(f.depths), len(cols)
+    start = np.asarray(t0, dtype=float)
+    if start.ndim == 0:
+        start = np.full(n, float(start))
+    if start.shape != (n,):
+        raise ValueError(f"t0 must be a scalar or one start time per requested column ({n})")
+    if not np.all(np.isfinite(start)):
+        raise ValueError("t0 must be finite")
+    f.to_device(device)
+    import torch
+    # re and im on the device; the host copy is made of them one after the other
+    need = 16 * R * n * nt
+    free = torch.cuda.mem_get_info(f.dev)[0]
+    if need > free:
+        raise ValueError(f"the signal needs {need} bytes of device memory ({R} x {n} x {nt} complex samples) and {free} "
+                         "are free: ask for fewer depths, columns or samples per call")
+    f.absorb(profile, boundary, counts=counts)                        # (one run of the boundary loss: weights and counts)
+    q = _phase_index(f, counts)
+    offsets, tube, _, T, _, I = _device_arrivals(f, cols)
+    G = R * n
+    # every arrival's phase index: q[column, tube], the column of its group's slot
+    group = torch.repeat_interleave(torch.arange(G, device=f.dev), offsets[1:] - offsets[:-1])
+    col = torch.from_numpy(cols.astype(np.int64)).to(f.dev)[group % n]
+    qa = q[col, tube.long()].contiguous()
+    if len(T) == 0:                                                   # (no arrivals at all: the entry refuses null pointers)
+        T, I = (torch.zeros(1, dtype=torch.float64, device=f.dev) for _ in range(2))
+        qa = torch.zeros(1, dtype=torch.int32, device=f.dev)
+    tstart = f.upload(np.tile(start, R))
+    re, im = (torch.empty((R, n, nt), dtype=torch.float64, device=f.dev) for _ in range(2))
+    _lib.signal_device(f.env.device, offsets.data_ptr(), G, T.data_ptr(), I.data_ptr(), qa.data_ptr(), tstart.data_ptr(), f0,
+                       rs, step, nt, re.data_ptr(), im.data_ptr(), f.stream)
+    at_source = np.flatnonzero(np.abs(np.asarray(f.x)[cols] - f.x[0]) == 0)
+    if len(at_source):                                                # the source's own column, as pressure_field has it
+        idx = torch.from_numpy(at_source).to(f.dev)
+        re[:, idx, :] = math.nan
+        im[:, idx, :] = math.nan
+    out = np.empty((R, n, nt), dtype=np.complex128)
+    out.real = re.cpu().numpy()
+    out.imag = im.cpu().numpy()
+    return out
+
+
+__all__ = ["received_signal", "pulse_sigma"]
