@@ -571,6 +571,10 @@ int pgr_boundary_loss_device(pgr_env* env, const double* bx, const double* bp, c
  * this ABI, stated in a file of its own beside this one. ---- */
 #include "pgr_signal.h"
 
+/* ---- Transfer function of the arrivals over a frequency band: pgr_spectrum_device.  Part of this
+ * ABI, stated in a file of its own beside this one. ---- */
+#include "pgr_spectrum.h"
+
 /* What this build of the library is: whether the instruction-layout pass of the build was applied
  * ("relaid: 502 -> 31 straddles ..." or "plain hipcc") and which arithmetic variant was compiled.
  * bench.py puts it into its JSON line so that a measured number names the binary it came from. */

@@ -109,6 +109,13 @@ try:
         SIGNAL_PROTOTYPES = parse_header(_f.read())[0]
 except OSError as _e:
     raise PgrError(f"{SIGNAL_HEADER}: the C ABI header cannot be read ({_e})") from None
+# ... and the transfer function of the arrivals over a frequency band, likewise
+SPECTRUM_HEADER = os.path.join(_HERE, "..", "include", "pgr_spectrum.h")
+try:
+    with open(SPECTRUM_HEADER) as _f:
+        SPECTRUM_PROTOTYPES = parse_header(_f.read())[0]
+except OSError as _e:
+    raise PgrError(f"{SPECTRUM_HEADER}: the C ABI header cannot be read ({_e})") from None
 globals().update(_CONSTANTS)   # PGR_TERMINATE_BACKWARDS, PGR_SAMPLE_MAJOR, ... PGR_OPT_D2H_REGISTER
 
 _REBUILD = "`python -c 'import __graft_entry__ as g; g.build()'`"
@@ -195,7 +202,7 @@ def build(force=False, verbose=False, out=None, extra_flags=()):
     src = os.path.join(CSRC, "pgr_hip.hip")
     hdr = os.path.join(_HERE, "..", "include", "pgr.h")
     # (one translation unit: pgr_hip.hip includes every csrc/*.h -- device building blocks, the fan kernel, the host side in pieces)
-    deps = [src, hdr, COHERENT_HEADER, SIGNAL_HEADER, os.path.join(_HERE, "_isa_layout.py")] + sorted(
+    deps = [src, hdr, COHERENT_HEADER, SIGNAL_HEADER, SPECTRUM_HEADER, os.path.join(_HERE, "_isa_layout.py")] + sorted(
         os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h"))
     if not force and os.path.exists(LIB_PATH):
         if os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(d) for d in deps):
@@ -259,11 +266,11 @@ def load():
                "pygenray_amd._lib.build_contracted()" if ARITH == "contracted" else "") +
             "). pygenray_amd has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**PROTOTYPES, **COHERENT_PROTOTYPES, **SIGNAL_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **COHERENT_PROTOTYPES, **SIGNAL_PROTOTYPES, **SPECTRUM_PROTOTYPES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError:
-            raise PgrError(f"{LIB_PATH} does not export {name}, which include/pgr.h declares (itself or through pgr_coherent.h / pgr_signal.h): the library is older than "
+            raise PgrError(f"{LIB_PATH} does not export {name}, which include/pgr.h declares (itself or through pgr_coherent.h / pgr_signal.h / pgr_spectrum.h): the library is older than "
                            f"the header. Rebuild it: {_REBUILD}.") from None
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -814,3 +821,16 @@ def signal_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, tstart_ptr
     offsets[g + 1]) at the times tstart[g] + n dt; see include/pgr_signal.h."""
     check(load().pgr_signal_device(int(device), offsets_ptr, int(n_groups), t_ptr, i_ptr, q_ptr or None, tstart_ptr,
                                    float(frequency), float(inv_sigma), float(dt), int(n_times), re_ptr, im_ptr, stream))
+
+
+def spectrum_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, l_ptr, tred_ptr, freq, alpha, re_ptr, im_ptr,
+                    stream=0):
+    """pgr_spectrum_device on raw device pointers (ints; q / l 0: absent) and the HOST sequences freq (Hz) and alpha (dB per
+    metre, or None; given exactly when l is): re / im [n_groups][len(freq)] = the transfer function of the arrivals T / I / q
+    / L of each group [offsets[g], offsets[g + 1]) at every frequency, reduced by tred[g]; see include/pgr_spectrum.h."""
+    fr = _c(freq).reshape(-1)
+    al = None if alpha is None else _c(alpha).reshape(-1)
+    if al is not None and len(al) != len(fr):
+        raise ValueError("freq and alpha must have equal length")
+    check(load().pgr_spectrum_device(int(device), offsets_ptr, int(n_groups), t_ptr, i_ptr, q_ptr or None, l_ptr or None,
+                                     tred_ptr, _addr(fr), _addr(al), len(fr), re_ptr, im_ptr, stream))

@@ -33,6 +33,65 @@ def _inv_sigma(bandwidth):
     return math.pi * B / math.sqrt(math.log(2.0))
 
 
+def _per_column(value, n, name, what):
+    """``value``, a scalar or one value per requested column -> float array (n,), finite (``name`` and ``what`` word the
+    errors)"""
+    v = np.asarray(value, dtype=float)
+    if v.ndim == 0:
+        v = np.full(n, float(v))
+    if v.shape != (n,):
+        raise ValueError(f"{name} must be a scalar or one {what} per requested column ({n})")
+    if not np.all(np.isfinite(v)):
+        raise ValueError(f"{name} must be finite")
+    return v
+
+
+def _check_fits(f, R, n, m, product, entries):
+    """``ValueError`` when re and im, (R, n, m) float64 each, do not fit in the free memory of the frame's device"""
+    import torch
+    # re and im on the device; the host copy is made of them one after the other
+    need = 16 * R * n * m
+    free = torch.cuda.mem_get_info(f.dev)[0]
+    if need > free:
+        raise ValueError(f"the {product} needs {need} bytes of device memory ({R} x {n} x {m} complex {entries}) and {free} "
+                         f"are free: ask for fewer depths, columns or {entries} per call")
+
+
+def _arrival_terms(f, cols, profile, boundary, counts):
+    """What the sums over a fan's arrivals take, left on the device of the frame `f` (a _FanFrame after to_device): the
+    weights of `profile` / `boundary`, the tubes' phase index and the arrivals at the save columns `cols` -> (offsets int64
+    [R * n + 1], tube int32, w, T, I float64, q int32, column int64), per arrival from `tube` on: q and column are the phase
+    index and the save column of the arrival's tube and group.  Without arrivals T, I and q hold one zero each (the entries
+    refuse null pointers)."""
+    import torch
+    f.absorb(profile, boundary, counts=counts)                        # (one run of the boundary loss: weights and counts)
+    q = _phase_index(f, counts)
+    offsets, tube, w, T, _, I = _device_arrivals(f, cols)
+    G, n = len(f.depths) * len(cols), len(cols)
+    # every arrival's phase index: q[column, tube], the column of its group's slot
+    group = torch.repeat_interleave(torch.arange(G, device=f.dev), offsets[1:] - offsets[:-1])
+    col = torch.from_numpy(cols.astype(np.int64)).to(f.dev)[group % n]
+    qa = q[col, tube.long()].contiguous()
+    if len(T) == 0:                                                   # (no arrivals at all: the entry refuses null pointers)
+        T, I = (torch.zeros(1, dtype=torch.float64, device=f.dev) for _ in range(2))
+        qa = torch.zeros(1, dtype=torch.int32, device=f.dev)
+    return offsets, tube, w, T, I, qa, col
+
+
+def _to_host(f, cols, re, im):
+    """re / im (R, n, m) on the device -> complex128 (R, n, m) on the host, re then im, the source's own columns NaN"""
+    import torch
+    at_source = np.flatnonzero(np.abs(np.asarray(f.x)[cols] - f.x[0]) == 0)
+    if len(at_source):                                                # the source's own column, as pressure_field has it
+        idx = torch.from_numpy(at_source).to(f.dev)
+        re[:, idx, :] = math.nan
+        im[:, idx, :] = math.nan
+    out = np.empty(tuple(re.shape), dtype=np.complex128)
+    out.real = re.cpu().numpy()
+    out.imag = im.cpu().numpy()
+    return out
+
+
 def received_signal(rays, receiver_depths, env, frequency, bandwidth, t0, dt, n_times, range_indices=None, absorption=None,
                     bottom_loss=None, surface_loss=None, flatearth=True, device=0):
     """The complex-demodulated signal of ``rays`` (a ``RayFan`` from ``shoot_rays``) at ``receiver_depths`` (metres, positive
@@ -50,7 +109,8 @@ def received_signal(rays, receiver_depths, env, frequency, bandwidth, t0, dt, n_
     with r = 0 is NaN, as in ``pressure_field``; where no arrival is within 8 sigma the signal is 0.
 
     ``absorption``, ``bottom_loss``, ``surface_loss``: the weights of ``transmission_loss``, exactly.  The absorption
-    weights are those of the one profile given, i.e. of the centre frequency: they are not varied across the band.  The
+    weights are those of the one profile given, i.e. of the centre frequency: they are not varied across the band
+    (``received_waveform`` with a callable ``absorption`` varies them).  The
     frame, the sound speed and the errors are ``pressure_field``'s (a fan with bounces needs its bounce log,
     ``shoot_rays(..., max_bounces=K)``).  ``ValueError`` when ``R * n * n_times`` complex samples do not fit in the free
     device memory, before any kernel runs.  A device-resident fan is processed where it is and stays device resident."""
@@ -72,45 +132,16 @@ def received_signal(rays, receiver_depths, env, frequency, bandwidth, t0, dt, n_
     counts = _needs_counts(rays)
     cols = _columns(range_indices, len(f.x))
     R, n = len(f.depths), len(cols)
-    start = np.asarray(t0, dtype=float)
-    if start.ndim == 0:
-        start = np.full(n, float(start))
-    if start.shape != (n,):
-        raise ValueError(f"t0 must be a scalar or one start time per requested column ({n})")
-    if not np.all(np.isfinite(start)):
-        raise ValueError("t0 must be finite")
+    start = _per_column(t0, n, "t0", "start time")
     f.to_device(device)
     import torch
-    # re and im on the device; the host copy is made of them one after the other
-    need = 16 * R * n * nt
-    free = torch.cuda.mem_get_info(f.dev)[0]
-    if need > free:
-        raise ValueError(f"the signal needs {need} bytes of device memory ({R} x {n} x {nt} complex samples) and {free} "
-                         "are free: ask for fewer depths, columns or samples per call")
-    f.absorb(profile, boundary, counts=counts)                        # (one run of the boundary loss: weights and counts)
-    q = _phase_index(f, counts)
-    offsets, tube, _, T, _, I = _device_arrivals(f, cols)
-    G = R * n
-    # every arrival's phase index: q[column, tube], the column of its group's slot
-    group = torch.repeat_interleave(torch.arange(G, device=f.dev), offsets[1:] - offsets[:-1])
-    col = torch.from_numpy(cols.astype(np.int64)).to(f.dev)[group % n]
-    qa = q[col, tube.long()].contiguous()
-    if len(T) == 0:                                                   # (no arrivals at all: the entry refuses null pointers)
-        T, I = (torch.zeros(1, dtype=torch.float64, device=f.dev) for _ in range(2))
-        qa = torch.zeros(1, dtype=torch.int32, device=f.dev)
+    _check_fits(f, R, n, nt, "signal", "samples")
+    offsets, _, _, T, I, qa, _ = _arrival_terms(f, cols, profile, boundary, counts)
     tstart = f.upload(np.tile(start, R))
     re, im = (torch.empty((R, n, nt), dtype=torch.float64, device=f.dev) for _ in range(2))
-    _lib.signal_device(f.env.device, offsets.data_ptr(), G, T.data_ptr(), I.data_ptr(), qa.data_ptr(), tstart.data_ptr(), f0,
+    _lib.signal_device(f.env.device, offsets.data_ptr(), R * n, T.data_ptr(), I.data_ptr(), qa.data_ptr(), tstart.data_ptr(), f0,
                        rs, step, nt, re.data_ptr(), im.data_ptr(), f.stream)
-    at_source = np.flatnonzero(np.abs(np.asarray(f.x)[cols] - f.x[0]) == 0)
-    if len(at_source):                                                # the source's own column, as pressure_field has it
-        idx = torch.from_numpy(at_source).to(f.dev)
-        re[:, idx, :] = math.nan
-        im[:, idx, :] = math.nan
-    out = np.empty((R, n, nt), dtype=np.complex128)
-    out.real = re.cpu().numpy()
-    out.imag = im.cpu().numpy()
-    return out
+    return _to_host(f, cols, re, im)
 
 
 __all__ = ["received_signal", "pulse_sigma"]
