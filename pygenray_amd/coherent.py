@@ -111,8 +111,10 @@ def pressure_field(rays, receiver_depths, env, frequency, absorption=None, botto
     ``caustic_index`` (-pi/2 per caustic) and n_surf its surface bounces so far (pi each: a pressure-release surface); the
     bottom is rigid, phase 0.  Summed tube by tube in launch order, so ``abs(p) ** 2`` is ``transmission_loss``'s
     intensity wherever one tube arrives.  A tube whose two rays have bounced a different number of times (folded over a
-    boundary) is left out: a strip about one tube wide along both boundaries is empty.  The tube spike at a caustic
-    remains.  ``absorption``, ``bottom_loss``, ``surface_loss``: the weights of ``transmission_loss``, exactly (amplitudes
+    boundary) is left out, and a bounce counts from the save range nearest to it, where the ray's sample before the bounce
+    is the reflected segment continued backwards, beyond the boundary: arrivals are missing in a strip up to
+    tan(theta_max) dx / 2 wide along both boundaries (dx the save step, theta_max the steepest ray's angle there), not
+    just one tube's width.  The tube spike at a caustic remains.  ``absorption``, ``bottom_loss``, ``surface_loss``: the weights of ``transmission_loss``, exactly (amplitudes
     take their square root through I).  The frame and the sound speed are ``transmission_loss``'s.  A fan with bounces
     needs its bounce log (``shoot_rays(..., max_bounces=K)``): ``ValueError`` otherwise.  A device-resident fan is
     processed where it is and stays device resident."""

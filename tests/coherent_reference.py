@@ -216,9 +216,10 @@ def log_counts(bx, bk, xf):
     return nb, ns
 
 
-def fan_pressure(rays, depths, environment, f, flatearth=True, W=None, nb=None, ns=None):
+def fan_pressure(rays, depths, environment, f, flatearth=True, W=None, nb=None, ns=None, q=None):
     """pressure_field's definition on a host fan: the frame and p0 as tl_reference.fan_intensity prepares them, q from the
-    restated caustic index and the per-sample counts nb / ns (M, S) (None: a fan without bounces) -> complex (R, S)"""
+    restated caustic index and the per-sample counts nb / ns (M, S) (None: a fan without bounces) -> complex (R, S).  A q
+    (M, S) given is used in place of the definition's (the tests' power checks: a deliberately wrong convention)."""
     from pygenray_amd.environment import _mirror_envi_arrays, _unpack_envi
     from pygenray_amd.host_physics import bilinear_interp
     from pygenray_amd.launch_rays import _initial_slowness
@@ -229,6 +230,7 @@ def fan_pressure(rays, depths, environment, f, flatearth=True, W=None, nb=None, 
         x = -x
     c_source = bilinear_interp(x[0], float(rays.source_depths[0]), rin, zin, cin)
     p0 = _initial_slowness(rays.thetas, c_source)
-    q = tube_phase(caustic_index(-np.asarray(rays.zs), nb, ns), nb, ns)
+    if q is None:
+        q = tube_phase(caustic_index(-np.asarray(rays.zs), nb, ns), nb, ns)
     re, im = tube_pressure(rays.zs, rays.ps, rays.ts, x, p0, depths, cin, rin, zin, W, q, f)
     return re + 1j * im
