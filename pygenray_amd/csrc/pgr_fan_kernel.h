@@ -474,14 +474,37 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
                 // what only the service needs of the environment descriptor and of the kernel arguments is read
                 // HERE, through pointers the compiler cannot trace back (the empty asm): hoisted to the prologue
                 // these values sit in SGPRs across the step loop and push loop values out to VGPR lanes
-                const EnvDev* es_p = env_p;
+                // (the descriptor is never written while a kernel runs: read through the constant address space these are
+                // scalar loads, whatever stores the kernel has made before)
+                typedef const EnvDev __attribute__((address_space(4))) EnvConst;
+                EnvConst* es_p = (EnvConst*)env_p;
                 asm volatile("" : "+s"(es_p));
-                const EnvDev& es = *es_p;
+                EnvConst& es = *es_p;
                 const char __attribute__((address_space(4))) * ks_p =
                     (const char __attribute__((address_space(4))) *)__builtin_amdgcn_kernarg_segment_ptr();
                 asm volatile("" : "+s"(ks_p));
                 const FanArgs __attribute__((address_space(4))) & as = *(const FanArgs __attribute__((address_space(4))) *)(ks_p + kFanArgsKernargOffset);
-                const double svc_c_lo = es.c_lo, svc_c_hi = es.c_hi;
+                // ONE batch of scalar loads at entry for everything the service reads of the two (rlo_tol ... c_hi are
+                // adjacent: one wide load), issued in front of Q, whose arithmetic covers their latency; the empty asm
+                // behind Q is their first use, so the loads cannot sink to the sections that need them (where a lone
+                // wave would wait out a scalar-cache round trip each time)
+                // SVC_BATCH: only the instances whose scalar file has room for the batch's 14 SGPRs across the service -- the
+                // LDS table on the dz = 1 grid, the headline family.  Everywhere else the register allocator paid for the
+                // batch with step-loop values spilled to VGPR lanes (v_readlane per use in the loop: the flat-earth end-state
+                // instance 5.79 -> 5.92 ms), so those instances read each value where it is used, as they always did.
+                constexpr bool SVC_BATCH = LDS_TAB && ZM == 4;
+                double svc_c_lo = es.c_lo, svc_c_hi = es.c_hi;
+                double svc_rlo_tol = 0, svc_rhi_tol = 0, svc_b_xlo = 0, svc_b_xhi = 0, svc_inv_dsave = 0;
+                int svc_beta_zero = 0;
+                uint32_t svc_flags = 0;
+                if (SVC_BATCH) {
+                    svc_rlo_tol = es.rlo_tol; svc_rhi_tol = es.rhi_tol;
+                    svc_b_xlo = es.b_xlo; svc_b_xhi = es.b_xhi;   // (= depth_ranges[0], depth_ranges[nb - 1]: pgr_env.h)
+                    svc_beta_zero = es.beta_zero;
+                    svc_flags = as.flags;
+                    if (save) svc_inv_dsave = as.inv_dsave;
+                }
+#define PGR_SVC(batched_, lazy_) (SVC_BATCH ? (batched_) : (lazy_))
                 if (pend && parked) {
                     parked = false;
                     const unsigned active = pk_active;
@@ -497,6 +520,9 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
                         (void)n0; (void)c_new; (void)es0; (void)es1; (void)es2;
                         PGR_FORM_Q();
                     }
+                    if (SVC_BATCH)
+                        asm volatile("" : "+s"(svc_c_lo), "+s"(svc_c_hi), "+s"(svc_rlo_tol), "+s"(svc_rhi_tol), "+s"(svc_b_xlo),
+                                          "+s"(svc_b_xhi), "+s"(svc_beta_zero), "+s"(svc_flags));
                     PGR_SSTAMP(1);    // Q
                     int ev = -1;
                     double best = 0;
@@ -544,7 +570,10 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
                             // safeguarded Newton: three steps in a row (quadratic convergence from the secant
                             // start: ~1e-3, 1e-6, 1e-12 of the step; the third one moves by less than the
                             // tolerance), more only for a lane that still moves
-                            for (int it = 0; it < 16; it++) {
+                            // (three straight-line steps and ONE test behind them; the steps beyond the third are a
+                            // rare block of their own, out of the common service's way)
+                            double ds = 0;
+                            auto newton_step = [&]() __attribute__((always_inline)) {
                                 double zs = y1 + h * (sN * (q0 + sN * (q1 + sN * (q2 + sN * q3))));
                                 double dz = h * (q0 + sN * (2 * q1 + sN * (3 * q2 + sN * 4 * q3)));
                                 double F = zs, dF = dz;
@@ -562,9 +591,17 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
                                 // (closed bracket: when F evaluates to exactly 0 the Newton step is
                                 // zero, sn == lo, and that is convergence, not an escape)
                                 if (!(sn >= lo && sn <= hi)) sn = 0.5 * (lo + hi);
-                                double ds = fabs(sn - sN);
+                                ds = fabs(sn - sN);
                                 sN = sn;
-                                if (it >= 2 && ballot64(ds * h >= 1e-12 * (1.0 + fabs(t))) == 0) break;
+                            };
+                            newton_step();
+                            newton_step();
+                            newton_step();
+                            if (__builtin_expect(ballot64(ds * h >= 1e-12 * (1.0 + fabs(t))) != 0, 0)) {
+                                for (int it = 3; it < 16; it++) {
+                                    newton_step();
+                                    if (ballot64(ds * h >= 1e-12 * (1.0 + fabs(t))) == 0) break;
+                                }
                             }
                             PGR_SSTAMP(3);    // Newton
                             const double xs = t + sN * h;
@@ -592,14 +629,15 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
            Q7): with 0 < c <= c_hi (the table's maximum, a margin for the extrapolated sliver above the        \
            surface included) |p| c_hi < 1 settles both from p alone -- no table look-up */                    \
         double pc_ = pz_;                                                                                        \
-        if (ballot64(!((svc_c_lo > 0) & (fabs(pz_) * svc_c_hi < 1.0))) != 0) {                                    \
+        if (__builtin_expect(ballot64(!((svc_c_lo > 0) & (fabs(pz_) * svc_c_hi < 1.0))) != 0, 0)) {               \
             double c_, cp_;                                                                                      \
             C.lookup((X_), z_, c_, cp_);                                                                         \
             pc_ = pz_ * c_;                                                                                      \
         }                                                                                                        \
         const double bd_ = any_bottom ? C.bathy(X_) : 0.0;                                                       \
         FIRED_ = bottom ? ((pc_ > 0) & (pc_ <= 1.0) & (z_ > bd_)) : ((z_ < 0) & (pc_ < 0) & (pc_ >= -1.0));       \
-        BBOX_ = (z_ > C.h_zhi_tol) | (z_ < C.h_zlo_tol) | ((X_) < es.rlo_tol) | ((X_) > es.rhi_tol);             \
+        BBOX_ = (z_ > C.h_zhi_tol) | (z_ < C.h_zlo_tol) | ((X_) < PGR_SVC(svc_rlo_tol, es.rlo_tol)) |             \
+                ((X_) > PGR_SVC(svc_rhi_tol, es.rhi_tol));                                                       \
     } while (0)
                             bool ga, gb, bbox_a, bbox_b;
                             PGR_TRUE_EVENT(xa, ga, bbox_a);
@@ -636,7 +674,7 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
                         // the bracket, fcur = the event at cur; it starts from cur = t_new (fired), xblk = t.
                         const double xtol = 4 * DBL_EPSILON, brtol = 4 * DBL_EPSILON;
                         double cur = t_new, xblk = t;
-                        bool fcur = true;
+                        int fcm = -1;   // the event at cur, as a mask (all ones: fired)
                         {
                             // phase 1: the halvings that can neither end the search nor take brentq's minimum
                             // step (|xblk - cur| / 2 stays above 4 delta), kept as (not fired end, fired end): 9
@@ -656,47 +694,91 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
                                     if (ballot64(n1 < m + bit) == 0) m += bit;
                                 n1 = m;
                             }
+                            // The select of a halving does not go through VCC (compare -> VCC -> v_cndmask is the slow link
+                            // of the chain): nw - xb is negative exactly when nw < xb (finite doubles; equal ones give +0 --
+                            // no operand is a zero: halvings are taken on steps with t > 0 or t_new < 0 only, `sterbenz`),
+                            // so the sign word shifted down IS the mask, and v_bfi_b32 selects with it.  The same
+                            // iterates by the same operations.  The count is wave-uniform: blocks of 8, then 4, 2, 1 --
+                            // one taken branch per 8 halvings instead of one per 4 and a rolled remainder.
                             double plo = t, phi = t_new;
-                            bool lastc = true;
-#pragma unroll 4
-                            for (int k = 0; k < n1; k++) {
+                            int lastm = -1;   // (all ones: the latest iterate fired)
+                            auto halving = [&]() __attribute__((always_inline)) {
                                 const double nw = __builtin_fma(phi - plo, 0.5, plo);  // (phi - plo) / 2 is exact: one rounding either way
-                                const bool ge = (nw >= xb), le = (nw <= xa);
-                                phi = ge ? nw : phi;
-                                plo = le ? nw : plo;
-                                lastc = ge | (lastc & !le);
+                                const int m_lt = pgr_sign_mask(nw - xb);   // all ones: nw < xb, i.e. not (nw >= xb)
+                                const int m_gt = pgr_sign_mask(xa - nw);   // all ones: nw > xa, i.e. not (nw <= xa)
+                                phi = pgr_mask_select(m_lt, phi, nw);
+                                plo = pgr_mask_select(m_gt, plo, nw);
+                                lastm = ~m_lt | (lastm & m_gt);
+                            };
+                            int k = n1;
+#pragma unroll 1
+                            for (; k >= 8; k -= 8) {
+                                halving(); halving(); halving(); halving(); halving(); halving(); halving(); halving();
                             }
-                            if (n1 > 0) { cur = lastc ? phi : plo; xblk = lastc ? plo : phi; fcur = lastc; }
+                            if (k & 4) { halving(); halving(); halving(); halving(); }
+                            if (k & 2) { halving(); halving(); }
+                            if (k & 1) halving();
+                            // (n1 == 0 leaves cur = t_new, xblk = t, fired: brentq's own start)
+                            cur = pgr_mask_select(lastm, phi, plo);
+                            xblk = pgr_mask_select(lastm, plo, phi);
+                            fcm = lastm;
                         }
                         PGR_SSTAMP(6);    // replay phase 1
                         // phase 2: brentq's loop as it stands (scipy/optimize/Zeros/brentq.c) for the last few
-                        // iterations, all lanes in lock step; the true event is evaluated (for the whole wave,
-                        // behind a uniform branch) whenever some lane's iterate lies inside the band, and
-                        // decides for those lanes.  A lane whose search has ended (|sbis| < delta) stands still.
-                        double fcv = fcur ? 1.0 : 0.0;  // the event at cur, as a number (a carried bool costs more)
-                        bool done = !live;
+                        // iterations.  A lane's iterates depend on nothing but the lane, so the lanes need not keep
+                        // step: runs of eight iterations decided by POSITION, straight-line (one not-taken exit test
+                        // each), in which a lane whose search has ended (|sbis| < delta) stands still and a lane whose
+                        // iterate lies inside the band holds it; behind a run, rarely, the true event for the lanes that
+                        // hold one (for the whole wave, behind a uniform branch), which decides for them.
+                        // The iteration's decisions are masks in vector registers, as in phase 1 (a compare that goes through
+                        // the condition register to a select or to scalar logic stalls a lone wave at every hop): the
+                        // differences' sign words, and ONE ballot per iteration for the exit.  |sbis| - delta, delta - |sbis|,
+                        // nw - xb and xa - nw are negative exactly where the comparison holds.  Phase 2 also runs on steps that
+                        // contain x = 0 (n1 == 0), so zeros can occur here: a difference is -0 only as (-0) - (+0).  nw is
+                        // never -0 (cur + step is -0 only if both are, and a lane whose step is -0 has sbis = 0 and is done),
+                        // so nw - xb cannot be; |sbis| - delta and delta - |sbis| cannot either (delta > 0).  Only xa - nw
+                        // can (xa = -0, nw = +0), where it sends the iterate to the true event, right wherever it is asked.  copysign(delta, sbis) is brentq's (sbis > 0 ? delta : -delta) for
+                        // every lane that moves (sbis = 0 ends the search).
+                        const int m_live = live ? -1 : 0;
+                        int m_done = ~m_live, m_in = 0;
+                        double nw = cur;
+                        // (`it` counts RUNS: up to 200 runs of eight, 1 600 iterations, before an unfinished lane falls
+                        // through to the exact bisection -- brentq itself needs ~55 from any step)
                         for (int it = 0; it < 200; it++) {
-                            const double dlt = (xtol + brtol * fabs(cur)) / 2;
-                            const double sbis = (xblk - cur) / 2;
-                            done = !live | (fabs(sbis) < dlt);
-                            if (ballot64(!done) == 0) break;
-                            const double nw = (fabs(sbis) > dlt) ? cur + sbis : cur + (sbis > 0 ? dlt : -dlt);
-                            const bool inside = !done & (nw > xa) & (nw < xb);
-                            double fnv = (nw >= xb) ? 1.0 : 0.0;
-                            if (ballot64(inside) != 0) {
+#pragma unroll
+                            for (int u = 0; u < 8; u++) {
+                                const double dlt = (xtol + brtol * fabs(cur)) / 2;
+                                const double sbis = (xblk - cur) / 2;
+                                const double asb = fabs(sbis);
+                                m_done = ~m_live | pgr_sign_mask(asb - dlt);                          // |sbis| < delta
+                                nw = cur + pgr_mask_select(pgr_sign_mask(dlt - asb), sbis, __builtin_copysign(dlt, sbis));
+                                const int m_ltb = pgr_sign_mask(nw - xb);                             // nw < xb
+                                m_in = ~m_done & pgr_sign_mask(xa - nw) & m_ltb;                      // xa < nw < xb
+                                const int m_go = ~(m_done | m_in);
+                                if (ballot64(m_go != 0) == 0) break;
+                                // (by position: fired from xb on)
+                                xblk = pgr_mask_select(m_go & (~m_ltb ^ fcm), cur, xblk);
+                                cur = pgr_mask_select(m_go, nw, cur);
+                                fcm = (~m_ltb & m_go) | (fcm & ~m_go);
+                            }
+                            // (after a full run `m_done` and `m_in` are those of the run's last iterate: a lane that held
+                            // an iterate then still holds it, a lane that moved is looked at again in the next run)
+                            if (__builtin_expect(ballot64(m_in != 0) != 0, 0)) {
                                 bool fired, bbox_q;
                                 PGR_TRUE_EVENT(nw, fired, bbox_q);
                                 (void)bbox_q;
-                                fnv = inside ? (fired ? 1.0 : 0.0) : fnv;
-                            }
-                            xblk = (!done & (fnv != fcv)) ? cur : xblk;
-                            cur = done ? cur : nw;
-                            fcv = done ? fcv : fnv;
+                                const int m_f = fired ? -1 : 0;
+                                xblk = pgr_mask_select(m_in & (m_f ^ fcm), cur, xblk);
+                                cur = pgr_mask_select(m_in, nw, cur);
+                                fcm = (m_f & m_in) | (fcm & ~m_in);
+                            } else if (ballot64(m_done == 0) == 0) break;
                         }
+                        const bool done = m_done != 0;
                         if (live && done) { best = cur; ev = bottom ? 1 : 0; }
                         PGR_SSTAMP(7);    // replay phase 2
                     }
-                    if (ev < 0) {
+                    // (rare, and out of the common service's way: one wave-uniform test, not a skipped block)
+                    if (__builtin_expect(ballot64(ev < 0) != 0, 0) && ev < 0) {
                         fallbacks++;
                         // handle_events + solve_event_equation, SCIPY/ivp.py:51-131: brentq(xtol =
                         // rtol = 4 EPS) on a +-1 step function == bisection (Q6).  All events are
@@ -765,12 +847,12 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
                             } else {
                                 // beta = interp1d(depth_ranges, bottom_angles, 'cubic')(x)
                                 const double* xr = es.depth_ranges;
-                                if (!(t >= xr[0] && t <= xr[es.nb - 1])) {
+                                if (!(t >= PGR_SVC(svc_b_xlo, es.b_xlo) && t <= PGR_SVC(svc_b_xhi, es.b_xhi))) {   // (xr[0], xr[nb - 1])
                                     status = PGR_RAY_BETA_RANGE;
                                     theta_b = 0;
                                 } else {
                                     double beta = 0.0;
-                                    if (!es.beta_zero) {
+                                    if (!PGR_SVC(svc_beta_zero, es.beta_zero)) {
                                         int i;
                                         double xi;
                                         if (es.b_uniform) {
@@ -790,7 +872,7 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
                             }
                             PGR_SSTAMP(12);   // reflection law (bottom: the angle's cubic)
                             if (status == RUNNING) {
-                                if ((as.flags & PGR_TERMINATE_BACKWARDS) && (fabs(theta_b) > 90))
+                                if ((PGR_SVC(svc_flags, as.flags) & PGR_TERMINATE_BACKWARDS) && (fabs(theta_b) > 90))
                                     status = PGR_RAY_BACKWARD;
                                 else {
                                     // (theta_b = -theta at the surface and on a flat floor: the sine of minus an arcsine, cheaply)
@@ -817,6 +899,7 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
                     }
                 }
                 PGR_SSTAMP(13);   // new slowness (sine), end of the bounce block
+                if (save && SVC_BATCH) asm volatile("" : "+s"(svc_inv_dsave));
                 if (status == RUNNING && need_init) {
                     // ---- fresh solve_ivp: RK45.__init__ (SCIPY/rk.py:84-104) ----
                     double c;
@@ -850,7 +933,7 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
                     rejected = false;
                     need_init = false;
                     if (save) {
-                        jnext = G.nearest(t, as.inv_dsave);
+                        jnext = G.nearest(t, PGR_SVC(svc_inv_dsave, as.inv_dsave));
                         rnext = G.at(jnext);
                     }
                     PGR_SSTAMP(16);   // restart: events, nearest save point
@@ -938,6 +1021,7 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
     }
     if (!PERSIST || !wave_queue) break;   // (a persistent instance launched without a queue is one packet per wave too)
     }   // (the packet loop)
+#undef PGR_SVC
 #undef Tp
 #undef Zp
 #undef Pp
