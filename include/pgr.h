@@ -575,6 +575,11 @@ int pgr_boundary_loss_device(pgr_env* env, const double* bx, const double* bp, c
  * ABI, stated in a file of its own beside this one. ---- */
 #include "pgr_spectrum.h"
 
+/* ---- The coherent sums with a lag per arrival, the bottom's complex reflection coefficient:
+ * pgr_fan_pressure_phi, pgr_pressure_device_phi, pgr_signal_device_phi, pgr_spectrum_device_phi.  Part of this ABI, stated in
+ * a file of its own beside this one. ---- */
+#include "pgr_reflection.h"
+
 /* What this build of the library is: whether the instruction-layout pass of the build was applied
  * ("relaid: 502 -> 31 straddles ..." or "plain hipcc") and which arithmetic variant was compiled.
  * bench.py puts it into its JSON line so that a measured number names the binary it came from. */

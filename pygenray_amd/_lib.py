@@ -116,6 +116,13 @@ try:
         SPECTRUM_PROTOTYPES = parse_header(_f.read())[0]
 except OSError as _e:
     raise PgrError(f"{SPECTRUM_HEADER}: the C ABI header cannot be read ({_e})") from None
+# ... and the coherent sums with a lag per arrival, the bottom's complex reflection coefficient, likewise
+REFLECTION_HEADER = os.path.join(_HERE, "..", "include", "pgr_reflection.h")
+try:
+    with open(REFLECTION_HEADER) as _f:
+        REFLECTION_PROTOTYPES = parse_header(_f.read())[0]
+except OSError as _e:
+    raise PgrError(f"{REFLECTION_HEADER}: the C ABI header cannot be read ({_e})") from None
 globals().update(_CONSTANTS)   # PGR_TERMINATE_BACKWARDS, PGR_SAMPLE_MAJOR, ... PGR_OPT_D2H_REGISTER
 
 _REBUILD = "`python -c 'import __graft_entry__ as g; g.build()'`"
@@ -202,7 +209,7 @@ def build(force=False, verbose=False, out=None, extra_flags=()):
     src = os.path.join(CSRC, "pgr_hip.hip")
     hdr = os.path.join(_HERE, "..", "include", "pgr.h")
     # (one translation unit: pgr_hip.hip includes every csrc/*.h -- device building blocks, the fan kernel, the host side in pieces)
-    deps = [src, hdr, COHERENT_HEADER, SIGNAL_HEADER, SPECTRUM_HEADER, os.path.join(_HERE, "_isa_layout.py")] + sorted(
+    deps = [src, hdr, COHERENT_HEADER, SIGNAL_HEADER, SPECTRUM_HEADER, REFLECTION_HEADER, os.path.join(_HERE, "_isa_layout.py")] + sorted(
         os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h"))
     if not force and os.path.exists(LIB_PATH):
         if os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(d) for d in deps):
@@ -266,11 +273,12 @@ def load():
                "pygenray_amd._lib.build_contracted()" if ARITH == "contracted" else "") +
             "). pygenray_amd has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**PROTOTYPES, **COHERENT_PROTOTYPES, **SIGNAL_PROTOTYPES, **SPECTRUM_PROTOTYPES}.items():
+    for name, (restype, argtypes) in {**PROTOTYPES, **COHERENT_PROTOTYPES, **SIGNAL_PROTOTYPES, **SPECTRUM_PROTOTYPES,
+                                      **REFLECTION_PROTOTYPES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError:
-            raise PgrError(f"{LIB_PATH} does not export {name}, which include/pgr.h declares (itself or through pgr_coherent.h / pgr_signal.h / pgr_spectrum.h): the library is older than "
+            raise PgrError(f"{LIB_PATH} does not export {name}, which include/pgr.h declares (itself or through pgr_coherent.h / pgr_signal.h / pgr_spectrum.h / pgr_reflection.h): the library is older than "
                            f"the header. Rebuild it: {_REBUILD}.") from None
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -622,6 +630,12 @@ class FanHandle:
         check(load().pgr_fan_pressure_w(self._h, p0_ptr, weights or None, q_ptr or None, float(frequency), depths_ptr,
                                         int(n_depths), re_ptr, im_ptr, stream))
 
+    def pressure_phi(self, p0_ptr, q_ptr, phi_ptr, frequency, depths_ptr, n_depths, re_ptr, im_ptr, stream=0, weights=0):
+        """pgr_fan_pressure_phi on raw device pointers (ints): ``pressure`` with phi [S][M] float64, the lag in cycles every
+        surviving ray has collected up to every save range (include/pgr_reflection.h); phi 0 is refused."""
+        check(load().pgr_fan_pressure_phi(self._h, p0_ptr, weights or None, q_ptr or None, phi_ptr or None, float(frequency),
+                                          depths_ptr, int(n_depths), re_ptr, im_ptr, stream))
+
     def close(self):
         if getattr(self, "_h", None):
             load().pgr_fan_destroy(self._h)
@@ -814,6 +828,15 @@ def pressure_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, 
                                        im_ptr, stream))
 
 
+def pressure_phi_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, q_ptr, phi_ptr, frequency, depths_ptr,
+                        n_depths, re_ptr, im_ptr, stream=0, weights=0):
+    """pgr_pressure_device_phi on raw device pointers (ints): ``pressure_device`` with phi [n_samples][n_rays] float64, the
+    rays' lag in cycles (include/pgr_reflection.h); phi 0 is refused."""
+    check(load().pgr_pressure_device_phi(env._h, t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr,
+                                         weights or None, q_ptr or None, phi_ptr or None, float(frequency), depths_ptr,
+                                         int(n_depths), re_ptr, im_ptr, stream))
+
+
 def signal_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, tstart_ptr, frequency, inv_sigma, dt, n_times, re_ptr,
                   im_ptr, stream=0):
     """pgr_signal_device on raw device pointers (ints; q 0: absent): re / im [n_groups][n_times] = the complex baseband signal
@@ -821,6 +844,15 @@ def signal_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, tstart_ptr
     offsets[g + 1]) at the times tstart[g] + n dt; see include/pgr_signal.h."""
     check(load().pgr_signal_device(int(device), offsets_ptr, int(n_groups), t_ptr, i_ptr, q_ptr or None, tstart_ptr,
                                    float(frequency), float(inv_sigma), float(dt), int(n_times), re_ptr, im_ptr, stream))
+
+
+def signal_phi_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, phi_ptr, tstart_ptr, frequency, inv_sigma, dt, n_times,
+                      re_ptr, im_ptr, stream=0):
+    """pgr_signal_device_phi on raw device pointers (ints): ``signal_device`` with phi float64, every arrival's lag in cycles
+    (include/pgr_reflection.h); phi 0 is refused."""
+    check(load().pgr_signal_device_phi(int(device), offsets_ptr, int(n_groups), t_ptr, i_ptr, q_ptr or None, phi_ptr or None,
+                                       tstart_ptr, float(frequency), float(inv_sigma), float(dt), int(n_times), re_ptr, im_ptr,
+                                       stream))
 
 
 def spectrum_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, l_ptr, tred_ptr, freq, alpha, re_ptr, im_ptr,
@@ -834,3 +866,15 @@ def spectrum_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, l_ptr, t
         raise ValueError("freq and alpha must have equal length")
     check(load().pgr_spectrum_device(int(device), offsets_ptr, int(n_groups), t_ptr, i_ptr, q_ptr or None, l_ptr or None,
                                      tred_ptr, _addr(fr), _addr(al), len(fr), re_ptr, im_ptr, stream))
+
+
+def spectrum_phi_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, phi_ptr, l_ptr, tred_ptr, freq, alpha, re_ptr, im_ptr,
+                        stream=0):
+    """pgr_spectrum_device_phi on raw device pointers (ints) and the HOST sequences freq and alpha: ``spectrum_device`` with phi
+    float64, every arrival's lag in cycles (include/pgr_reflection.h); phi 0 is refused."""
+    fr = _c(freq).reshape(-1)
+    al = None if alpha is None else _c(alpha).reshape(-1)
+    if al is not None and len(al) != len(fr):
+        raise ValueError("freq and alpha must have equal length")
+    check(load().pgr_spectrum_device_phi(int(device), offsets_ptr, int(n_groups), t_ptr, i_ptr, q_ptr or None, phi_ptr or None,
+                                         l_ptr or None, tred_ptr, _addr(fr), _addr(al), len(fr), re_ptr, im_ptr, stream))

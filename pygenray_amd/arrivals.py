@@ -7,7 +7,7 @@ already are -- in HBM for a device-resident fan, uploaded through torch for a ho
 import numpy as np
 
 from .ray_objects import _columns
-from .transmission import _FanFrame, _absorption_profile, _boundary_spec
+from .transmission import _FanFrame, _absorption_profile, _boundary_spec, _lag_spec
 
 
 def _bilinear(x, y, x_grid, y_grid, values):
@@ -47,12 +47,18 @@ class Arrivals:
       which the ``Arrivals`` of ``arrivals()`` therefore keeps alive (a device-resident fan stays so); ``ValueError`` as
       ``caustic_index`` raises it (a fan with bounces and no bounce log), and for an ``Arrivals`` built without its fan.
 
+    - ``bottom_phase``: the lag in cycles the arrival has collected at its bottom bounces, -arg R / 2 pi summed over them (the
+      arrival adds exp(-2 pi i bottom_phase) in ``pressure_field``'s convention), when ``arrivals(..., bottom_loss=<a
+      BottomReflection>)`` made the object: the edge rays' lags interpolated by ``w``, Phi_k + w (Phi_k+1 - Phi_k).  ``None``
+      otherwise.
+
     Bounce counts are known only at a ray's end: at the fan's last column, ``rays.n_surfs[tube]`` and
     ``rays.n_botts[tube]`` apply.  The source's own column (r = 0) has no arrivals."""
 
     def __init__(self, offsets, receiver_depths, ranges, range_indices, tube, w, time, p, intensity, thetas, c_rx,
-                 turning_points=None):
+                 turning_points=None, *, bottom_phase=None):
         self.turning_points = turning_points
+        self.bottom_phase = bottom_phase
         self.offsets = offsets
         self.receiver_depths = receiver_depths
         self.ranges = ranges
@@ -172,7 +178,8 @@ def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=N
     one trajectory array of device memory for the duration of the call.
 
     ``bottom_loss`` / ``surface_loss``: boundary reflection loss as in ``transmission_loss``, one more factor of the same
-    weights (None and None, the default: exactly the call without them; a fan with a bounce log otherwise).
+    weights (None and None, the default: exactly the call without them; a fan with a bounce log otherwise).  A
+    ``BottomReflection`` as ``bottom_loss`` weights by its magnitude and also fills ``Arrivals.bottom_phase``.
 
     The ``Arrivals`` returned keeps a reference to ``rays`` and ``environment`` for its lazily computed ``caustics``: a
     device-resident fan's HBM stays allocated while the ``Arrivals`` lives, unless the fan is fetched (``to_host()``) or
@@ -185,6 +192,14 @@ def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=N
     f.to_device(device).absorb(profile, boundary)
     R, n = len(f.depths), len(cols)
     offsets, tube, w, T, P, I = _device_arrivals(f, cols)
+    phase = None
+    lag = _lag_spec(bottom_loss)
+    if lag is not None:
+        import torch
+        from .signal import _arrival_lags
+        group = torch.repeat_interleave(torch.arange(R * n, device=f.dev), offsets[1:] - offsets[:-1])
+        col = torch.from_numpy(cols.astype(np.int64)).to(f.dev)[group % n]
+        phase = _arrival_lags(f, lag, col, tube, w).cpu().numpy() if len(tube) else np.zeros(0)
     cin, rin, zin = f.tables
     xs = f.xf[cols]
     c_rx = _bilinear(np.broadcast_to(xs[None, :], (R, n)), np.broadcast_to(f.depths[:, None], (R, n)), rin, zin, cin)
@@ -195,7 +210,7 @@ def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=N
     turns = np.stack([turns[tube, slot], turns[tube + 1, slot]], axis=1)
     out = Arrivals(offsets, f.depths, np.asarray(f.x)[cols], cols.astype(np.int64), tube,
                    w.cpu().numpy(), T.cpu().numpy(), P.cpu().numpy(), I.cpu().numpy(), np.asarray(rays.thetas, dtype=float),
-                   c_rx, turns)
+                   c_rx, turns, bottom_phase=phase)
     out._source = (rays, environment, flatearth, device)
     return out
 

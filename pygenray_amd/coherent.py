@@ -8,8 +8,8 @@ fan, uploaded through torch for a host fan.  There is no CPU path.
 import numpy as np
 
 from . import _lib
-from .transmission import (_FanFrame, _TracedFan, _absorption_profile, _boundary_spec, _check_flatearth, _loss_table, _ptr,
-                           _save_grid)
+from .transmission import (_FanFrame, _TracedFan, _absorption_profile, _boundary_spec, _check_flatearth, _lag_spec,
+                           _loss_table, _ptr, _save_grid)
 
 
 def _needs_counts(rays):
@@ -109,7 +109,10 @@ def pressure_field(rays, receiver_depths, env, frequency, absorption=None, botto
 
     with the arrival's own intensity I and travel time T (interpolated across the tube), kappa the tube's
     ``caustic_index`` (-pi/2 per caustic) and n_surf its surface bounces so far (pi each: a pressure-release surface); the
-    bottom is rigid, phase 0.  Summed tube by tube in launch order, so ``abs(p) ** 2`` is ``transmission_loss``'s
+    bottom is rigid, phase 0, unless ``bottom_loss`` is a ``BottomReflection`` (``fluid_halfspace(...)``, or a table from
+    elsewhere): every bottom bounce then also turns the phase by arg R at its grazing angle -- the term gains
+    exp(-2 pi i phi), phi the lag in cycles the tube's two rays have collected at their bottom bounces so far (the bounce
+    post-pass run once more on the table's lag), interpolated across the tube as T is.  Summed tube by tube in launch order, so ``abs(p) ** 2`` is ``transmission_loss``'s
     intensity wherever one tube arrives.  A tube whose two rays have bounced a different number of times (folded over a
     boundary) is left out, and a bounce counts from the save range nearest to it, where the ray's sample before the bounce
     is the reflected segment continued backwards, beyond the boundary: arrivals are missing in a strip up to
@@ -128,8 +131,14 @@ def pressure_field(rays, receiver_depths, env, frequency, absorption=None, botto
     f.to_device(device).absorb(profile, boundary, counts=counts)      # (one run of the boundary loss: weights and counts)
     import torch
     q = _phase_index(f, counts)
+    lag = _lag_spec(bottom_loss)
     re, im = f.image(), f.image()
-    f.run("pressure", q.data_ptr(), f0, f.d_depths.data_ptr(), len(f.depths), re.data_ptr(), im.data_ptr())
+    if lag is None:
+        f.run("pressure", q.data_ptr(), f0, f.d_depths.data_ptr(), len(f.depths), re.data_ptr(), im.data_ptr())
+    else:
+        phi = f.boundary_loss(lag)                                        # (S, M): the post-pass once more, lags for dB
+        f.run("pressure_phi", q.data_ptr(), phi.data_ptr(), f0, f.d_depths.data_ptr(), len(f.depths), re.data_ptr(),
+              im.data_ptr())
     return torch.complex(re, im).cpu().numpy()
 
 

@@ -105,37 +105,9 @@ struct CohOut {
 
 __global__ void __launch_bounds__(64) pgr_coh_sum(EnvDev env, TlArgs a, CohOut o)
 {
-    __shared__ TlTubes L;
-    __shared__ TlRays Y;
-    const TlBand b = tl_band<false>(a);
-    double re = 0.0, im = 0.0;
-    if (b.r == 0.0) {                              // the source's own column (uniform in the wave)
-        re = NAN;
-        im = NAN;
-    } else {
-        const Ctx<false, 0> C(env, nullptr);
-        const int32_t* q = o.q ? o.q + (int64_t)b.s * a.M : nullptr;
-        tl_walk<true>(a, C, b, L, &Y, [&](int64_t c, int u) {
-            const int qk = q ? q[c * TL_TUBES + u] : 0;
-            if (qk < 0) return;
-            const double d0 = Y.d[u], d1 = Y.d[u + 1];
-            const double w = fdiv(b.d - d0, d1 - d0);
-            const double T = Y.T[u] + w * (Y.T[u + 1] - Y.T[u]);
-            const double amp = fsqrt(L.I[u]);
-            double y = o.f * T;
-            y = y - rint(y);
-            double t = y - 0.25 * (double)(qk & 3);
-            t = t - rint(t);
-            double cv, sv;
-            gcossin2pi(t, cv, sv);                 // (gcos2pi(t) and gsin2pi(t), their common part formed once)
-            re = re + amp * cv;
-            im = im + amp * sv;
-        });
-    }
-    if (b.rcv) {
-        o.re[b.j * a.S + b.s] = re;
-        o.im[b.j * a.S + b.s] = im;
-    }
+#define COH_PHI 0
+#include "pgr_coh_sum_body.h"
+#undef COH_PHI
 }
 
 static int coh_check(const double* re, const double* im, double f, const char* who)

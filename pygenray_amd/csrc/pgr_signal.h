@@ -64,75 +64,17 @@ __device__ __forceinline__ double sig_lane(double v, int u)
 
 __global__ void __launch_bounds__(64) pgr_sig_sum(SigArgs s)
 {
-    const int64_t g = blockIdx.x;
-    const int32_t n0 = (int32_t)blockIdx.y * SIG_TILE;          // (n0 < nt: the grid has ceil(nt / SIG_TILE) tiles)
-    const int lane = threadIdx.x;
-    const int64_t a_end = s.off[g + 1];
-    const double t0 = s.tstart[g];
-    const int32_t last = min(n0 + SIG_TILE - 1, s.nt - 1);
-    const double tA = sig_time(t0, n0, s.dt), tB = sig_time(t0, last, s.dt);
-    double t[SIG_ROWS], re[SIG_ROWS], im[SIG_ROWS];
-#pragma unroll
-    for (int i = 0; i < SIG_ROWS; i++) {
-        t[i] = sig_time(t0, min(n0 + i * 64 + lane, s.nt - 1), s.dt);
-        re[i] = 0.0;
-        im[i] = 0.0;
-    }
-    for (int64_t a0 = s.off[g]; a0 < a_end; a0 += 64) {
-        const int64_t a = a0 + lane;
-        double Ta = NAN, C = 0.0, Sn = 0.0;
-        bool live = false;
-        if (a < a_end) {
-            const int qa = s.q ? s.q[a] : 0;
-            Ta = s.T[a];
-            const double xA = (tA - Ta) * s.rs, xB = (tB - Ta) * s.rs;
-            const double vA = xA * xA, vB = xB * xB;
-            // the arrival before the tile, inside it, behind it; a NaN T fails all three
-            live = qa >= 0 && ((xA > 0.0 && vA <= 64.0) || (xA <= 0.0 && xB >= 0.0) || (xB < 0.0 && vB <= 64.0));
-            if (live) {
-                const double amp = fsqrt(s.I[a]);
-                double y = s.f * Ta;
-                y = y - rint(y);
-                double ph = y - 0.25 * (double)(qa & 3);
-                ph = ph - rint(ph);
-                double cv, sv;
-                gcossin2pi(ph, cv, sv);
-                C = amp * cv;
-                Sn = amp * sv;
-            }
-        }
-        uint64_t todo = __ballot(live);
-        while (todo) {                                          // uniform in the wave: increasing a
-            const int u = __builtin_ctzll(todo);
-            todo &= todo - 1;
-            const double Tu = sig_lane(Ta, u), Cu = sig_lane(C, u), Su = sig_lane(Sn, u);
-#pragma unroll
-            for (int i = 0; i < SIG_ROWS; i++) {
-                const double x = (t[i] - Tu) * s.rs;
-                const double v = x * x;
-                if (v <= 64.0) {
-                    const double E = gexp(-0.5 * v);
-                    re[i] = re[i] + Cu * E;
-                    im[i] = im[i] + Su * E;
-                }
-            }
-        }
-    }
-#pragma unroll
-    for (int i = 0; i < SIG_ROWS; i++) {
-        const int32_t n = n0 + i * 64 + lane;
-        if (n < s.nt) {
-            s.re[g * s.nt + n] = re[i];
-            s.im[g * s.nt + n] = im[i];
-        }
-    }
+#define SIG_PHI 0
+#include "pgr_sig_sum_body.h"
+#undef SIG_PHI
 }
 
-extern "C" int pgr_signal_device(int device, const int64_t* offsets, int64_t n_groups, const double* T, const double* I,
-                                 const int32_t* q, const double* tstart, double frequency, double inv_sigma, double dt,
-                                 int32_t n_times, double* re, double* im, void* stream)
+// both entries: the checks, then `sum` (pgr_sig_sum, or with phi pgr_sig_sum_phi) over (group, tile of samples)
+template <typename... Extra>
+static int sig_run(const char* who, int device, const int64_t* offsets, int64_t n_groups, const double* T, const double* I,
+                   const int32_t* q, const double* tstart, double frequency, double inv_sigma, double dt, int32_t n_times,
+                   double* re, double* im, void* stream, void (*sum)(SigArgs, Extra...), Extra... extra)
 {
-    const char* who = "pgr_signal_device";
     if (!offsets || !T || !I || !tstart || !re || !im) return fail(std::string(who) + ": null argument");
     if (n_groups < 1) return fail(std::string(who) + ": n_groups must be >= 1");
     if (n_groups > INT32_MAX) return fail(std::string(who) + ": too many groups");
@@ -144,10 +86,18 @@ extern "C" int pgr_signal_device(int device, const int64_t* offsets, int64_t n_g
     if (!std::isfinite(dt) || !(dt > 0.0)) return fail(std::string(who) + ": dt must be finite and > 0");
     HIPCHK(hipSetDevice(device));
     const SigArgs s{offsets, T, I, q, tstart, frequency, inv_sigma, dt, n_times, re, im};
-    hipLaunchKernelGGL(pgr_sig_sum, dim3((unsigned)n_groups, (unsigned)tiles), dim3(64), 0, (hipStream_t)stream, s);
+    hipLaunchKernelGGL(sum, dim3((unsigned)n_groups, (unsigned)tiles), dim3(64), 0, (hipStream_t)stream, s, extra...);
     const hipError_t e = hipGetLastError();
     if (e != hipSuccess) return fail(std::string(who) + ": launch failed: " + hipGetErrorString(e));
     return 0;
+}
+
+extern "C" int pgr_signal_device(int device, const int64_t* offsets, int64_t n_groups, const double* T, const double* I,
+                                 const int32_t* q, const double* tstart, double frequency, double inv_sigma, double dt,
+                                 int32_t n_times, double* re, double* im, void* stream)
+{
+    return sig_run("pgr_signal_device", device, offsets, n_groups, T, I, q, tstart, frequency, inv_sigma, dt, n_times, re, im,
+                   stream, pgr_sig_sum);
 }
 
 #endif  // PGR_SIGNAL_H

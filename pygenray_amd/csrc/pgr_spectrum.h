@@ -49,8 +49,11 @@ struct SpecArgs {
     double* im;               // [G][nf]
 };
 
-template <bool ABSORB>
-__device__ __forceinline__ void spec_sum(const SpecArgs& s)
+// PHI (pgr_spec_sum_phi): every arrival is turned back by its lag phi[a] in cycles, whose r = phi - rint(phi)
+// lane l forms where it stages the arrival and sig_lane broadcasts with the other constants; without it the instructions are
+// pgr_spec_sum's as they ever were.
+template <bool ABSORB, bool PHI>
+__device__ __forceinline__ void spec_sum(const SpecArgs& s, const double* phi)
 {
     const int64_t g = blockIdx.x;
     const int32_t k0 = (int32_t)blockIdx.y * SPEC_TILE;         // (k0 < nf: the grid has ceil(nf / SPEC_TILE) tiles)
@@ -68,7 +71,7 @@ __device__ __forceinline__ void spec_sum(const SpecArgs& s)
     }
     for (int64_t a0 = s.off[g]; a0 < a_end; a0 += 64) {
         const int64_t a = a0 + lane;
-        double tau = 0.0, amp = 0.0, qc = 0.0, La = 0.0;
+        double tau = 0.0, amp = 0.0, qc = 0.0, La = 0.0, rc = 0.0;
         bool live = false;
         if (a < a_end) {
             const int qa = s.q ? s.q[a] : 0;
@@ -77,6 +80,10 @@ __device__ __forceinline__ void spec_sum(const SpecArgs& s)
             amp = fsqrt(s.I[a]);
             qc = 0.25 * (double)(qa & 3);
             if (ABSORB) La = s.L[a];
+            if (PHI) {
+                const double pa = phi[a];
+                rc = pa - rint(pa);
+            }
         }
         uint64_t todo = __ballot(live);
         while (todo) {                                          // uniform in the wave: increasing a
@@ -84,12 +91,17 @@ __device__ __forceinline__ void spec_sum(const SpecArgs& s)
             todo &= todo - 1;
             const double tu = sig_lane(tau, u), au = sig_lane(amp, u), qu = sig_lane(qc, u);
             const double Lu = ABSORB ? sig_lane(La, u) : 0.0;
+            const double ru = PHI ? sig_lane(rc, u) : 0.0;
 #pragma unroll
             for (int i = 0; i < SPEC_ROWS; i++) {
                 double y = fk[i] * tu;
                 y = y - rint(y);
                 double ph = y - qu;
                 ph = ph - rint(ph);
+                if (PHI) {
+                    ph = ph - ru;
+                    ph = ph - rint(ph);
+                }
                 double cv, sv;
                 gcossin2pi(ph, cv, sv);
                 if (ABSORB) {
@@ -116,15 +128,25 @@ __device__ __forceinline__ void spec_sum(const SpecArgs& s)
 
 __global__ void __launch_bounds__(64) pgr_spec_sum(SpecArgs s)
 {
-    if (s.alpha) spec_sum<true>(s);                             // (uniform in the grid)
-    else spec_sum<false>(s);
+    if (s.alpha) spec_sum<true, false>(s, nullptr);             // (uniform in the grid)
+    else spec_sum<false, false>(s, nullptr);
 }
 
-extern "C" int pgr_spectrum_device(int device, const int64_t* offsets, int64_t n_groups, const double* T, const double* I,
-                                   const int32_t* q, const double* L, const double* tred, const double* freq,
-                                   const double* alpha, int32_t n_freq, double* re, double* im, void* stream)
+// pgr_spectrum_device_phi's sum (include/pgr_reflection.h)
+__global__ void __launch_bounds__(64) pgr_spec_sum_phi(SpecArgs s, const double* phi)
 {
-    const char* who = "pgr_spectrum_device";
+    if (s.alpha) spec_sum<true, true>(s, phi);                  // (uniform in the grid)
+    else spec_sum<false, true>(s, phi);
+}
+
+// both entries: the checks, the frequencies' device copy, then `sum` (pgr_spec_sum, or with phi pgr_spec_sum_phi) over (group,
+// tile of frequencies)
+template <typename... Extra>
+static int spec_run(const char* who, int device, const int64_t* offsets, int64_t n_groups, const double* T, const double* I,
+                    const int32_t* q, const double* L, const double* tred, const double* freq, const double* alpha,
+                    int32_t n_freq, double* re, double* im, void* stream, void (*sum)(SpecArgs, Extra...), Extra... extra)
+{
+
     if (!offsets || !T || !I || !tred || !freq || !re || !im) return fail(std::string(who) + ": null argument");
     if ((L != nullptr) != (alpha != nullptr))
         return fail(std::string(who) + ": L (the arrivals' path lengths) and alpha go together: give both or neither");
@@ -151,12 +173,30 @@ extern "C" int pgr_spectrum_device(int device, const int64_t* offsets, int64_t n
     const SpecArgs s{offsets, T, I, q, L, tred, d_freq, alpha ? d_freq + nf : nullptr, n_freq, re, im};
     hipError_t e = hipMemcpyAsync(b, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice, st);
     if (e == hipSuccess) {
-        hipLaunchKernelGGL(pgr_spec_sum, dim3((unsigned)n_groups, (unsigned)tiles), dim3(64), 0, st, s);
+        hipLaunchKernelGGL(sum, dim3((unsigned)n_groups, (unsigned)tiles), dim3(64), 0, st, s, extra...);
         e = hipGetLastError();
     }
     (void)hipFreeAsync(b, st);
     if (e != hipSuccess) return fail(std::string(who) + ": launch failed: " + hipGetErrorString(e));
     return 0;
+}
+
+extern "C" int pgr_spectrum_device(int device, const int64_t* offsets, int64_t n_groups, const double* T, const double* I,
+                                   const int32_t* q, const double* L, const double* tred, const double* freq,
+                                   const double* alpha, int32_t n_freq, double* re, double* im, void* stream)
+{
+    return spec_run("pgr_spectrum_device", device, offsets, n_groups, T, I, q, L, tred, freq, alpha, n_freq, re, im, stream,
+                    pgr_spec_sum);
+}
+
+extern "C" int pgr_spectrum_device_phi(int device, const int64_t* offsets, int64_t n_groups, const double* T, const double* I,
+                                       const int32_t* q, const double* phi, const double* L, const double* tred,
+                                       const double* freq, const double* alpha, int32_t n_freq, double* re, double* im,
+                                       void* stream)
+{
+    const char* who = "pgr_spectrum_device_phi";
+    if (!phi) return fail(std::string(who) + ": null phi (pgr_spectrum_device is the entry without it)");
+    return spec_run(who, device, offsets, n_groups, T, I, q, L, tred, freq, alpha, n_freq, re, im, stream, pgr_spec_sum_phi, phi);
 }
 
 #endif  // PGR_SPECTRUM_H

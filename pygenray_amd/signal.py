@@ -13,7 +13,7 @@ from . import _lib
 from .arrivals import _device_arrivals
 from .coherent import _needs_counts, _phase_index
 from .ray_objects import _columns
-from .transmission import _FanFrame, _absorption_profile, _boundary_spec
+from .transmission import _FanFrame, _absorption_profile, _boundary_spec, _lag_spec
 
 
 def pulse_sigma(bandwidth):
@@ -57,12 +57,25 @@ def _check_fits(f, R, n, m, product, entries):
                          f"are free: ask for fewer depths, columns or {entries} per call")
 
 
-def _arrival_terms(f, cols, profile, boundary, counts):
+def _arrival_lags(f, lag, col, tube, w):
+    """phi_a of every arrival, on the device: the lag in cycles of the tube's two edge rays at the arrival's column -- the
+    boundary post-pass on the tables `lag` of _lag_spec -- interpolated by the arrival's w in three separate operations,
+    Phi_k + w (Phi_k+1 - Phi_k), as pgr_coh_sum_phi forms it"""
+    Phi = f.boundary_loss(lag)                                        # (S, M)
+    k = tube.long()
+    P0, P1 = Phi[col, k], Phi[col, k + 1]
+    d = P1 - P0
+    d = w * d
+    return P0 + d
+
+
+def _arrival_terms(f, cols, profile, boundary, counts, lag=None):
     """What the sums over a fan's arrivals take, left on the device of the frame `f` (a _FanFrame after to_device): the
     weights of `profile` / `boundary`, the tubes' phase index and the arrivals at the save columns `cols` -> (offsets int64
     [R * n + 1], tube int32, w, T, I float64, q int32, column int64), per arrival from `tube` on: q and column are the phase
     index and the save column of the arrival's tube and group.  Without arrivals T, I and q hold one zero each (the entries
-    refuse null pointers)."""
+    refuse null pointers).  With `lag` (the tables of _lag_spec) one more element follows: phi float64, every arrival's
+    bottom lag in cycles (one zero without arrivals)."""
     import torch
     f.absorb(profile, boundary, counts=counts)                        # (one run of the boundary loss: weights and counts)
     q = _phase_index(f, counts)
@@ -75,6 +88,9 @@ def _arrival_terms(f, cols, profile, boundary, counts):
     if len(T) == 0:                                                   # (no arrivals at all: the entry refuses null pointers)
         T, I = (torch.zeros(1, dtype=torch.float64, device=f.dev) for _ in range(2))
         qa = torch.zeros(1, dtype=torch.int32, device=f.dev)
+    if lag is not None:
+        phi = _arrival_lags(f, lag, col, tube, w) if len(tube) else torch.zeros(1, dtype=torch.float64, device=f.dev)
+        return offsets, tube, w, T, I, qa, col, phi.contiguous()
     return offsets, tube, w, T, I, qa, col
 
 
@@ -108,7 +124,8 @@ def received_signal(rays, receiver_depths, env, frequency, bandwidth, t0, dt, n_
     convention.  ``bandwidth=0`` is the CW limit: every sample equals ``pressure_field(...)[j, column]``.  A requested column
     with r = 0 is NaN, as in ``pressure_field``; where no arrival is within 8 sigma the signal is 0.
 
-    ``absorption``, ``bottom_loss``, ``surface_loss``: the weights of ``transmission_loss``, exactly.  The absorption
+    ``absorption``, ``bottom_loss``, ``surface_loss``: the weights of ``transmission_loss``, exactly; a ``BottomReflection``
+    as ``bottom_loss`` also turns every arrival by its bottom bounces' phase, as in ``pressure_field``.  The absorption
     weights are those of the one profile given, i.e. of the centre frequency: they are not varied across the band
     (``received_waveform`` with a callable ``absorption`` varies them).  The
     frame, the sound speed and the errors are ``pressure_field``'s (a fan with bounces needs its bounce log,
@@ -136,11 +153,16 @@ def received_signal(rays, receiver_depths, env, frequency, bandwidth, t0, dt, n_
     f.to_device(device)
     import torch
     _check_fits(f, R, n, nt, "signal", "samples")
-    offsets, _, _, T, I, qa, _ = _arrival_terms(f, cols, profile, boundary, counts)
+    lag = _lag_spec(bottom_loss)
+    offsets, _, _, T, I, qa, _, *phi = _arrival_terms(f, cols, profile, boundary, counts, lag)
     tstart = f.upload(np.tile(start, R))
     re, im = (torch.empty((R, n, nt), dtype=torch.float64, device=f.dev) for _ in range(2))
-    _lib.signal_device(f.env.device, offsets.data_ptr(), R * n, T.data_ptr(), I.data_ptr(), qa.data_ptr(), tstart.data_ptr(), f0,
-                       rs, step, nt, re.data_ptr(), im.data_ptr(), f.stream)
+    if lag is None:
+        _lib.signal_device(f.env.device, offsets.data_ptr(), R * n, T.data_ptr(), I.data_ptr(), qa.data_ptr(), tstart.data_ptr(),
+                           f0, rs, step, nt, re.data_ptr(), im.data_ptr(), f.stream)
+    else:
+        _lib.signal_phi_device(f.env.device, offsets.data_ptr(), R * n, T.data_ptr(), I.data_ptr(), qa.data_ptr(),
+                               phi[0].data_ptr(), tstart.data_ptr(), f0, rs, step, nt, re.data_ptr(), im.data_ptr(), f.stream)
     return _to_host(f, cols, re, im)
 
 

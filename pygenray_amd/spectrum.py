@@ -13,7 +13,7 @@ from . import _lib
 from .coherent import _needs_counts
 from .ray_objects import _columns
 from .signal import _arrival_terms, _check_fits, _per_column, _to_host
-from .transmission import _FanFrame, _absorption_profile, _boundary_spec
+from .transmission import _FanFrame, _absorption_profile, _boundary_spec, _lag_spec
 
 
 def _band_absorption(absorption, freq):
@@ -60,7 +60,9 @@ def transfer_function(rays, receiver_depths, env, frequencies, range_indices=Non
     W(f) = 10^(-alpha(f) L / 20), alpha = ``absorption(frequencies) / 1000`` dB/m (its result must have the frequencies' shape
     and be finite and >= 0; its own errors propagate: ``thorp_absorption`` refuses f = 0) and L the arrival's path length,
     ``path_length`` interpolated across the tube as the travel time is.  ``bottom_loss``, ``surface_loss``: the weights of
-    ``transmission_loss``, with any ``absorption``.  The frame, the sound speed and the errors are ``pressure_field``'s (a fan
+    ``transmission_loss``, with any ``absorption``; a ``BottomReflection`` as ``bottom_loss`` also turns every arrival by its
+    bottom bounces' phase, as in ``pressure_field`` -- one table across the band: the plane-wave coefficient of
+    ``fluid_halfspace`` does not depend on frequency.  The frame, the sound speed and the errors are ``pressure_field``'s (a fan
     with bounces needs its bounce log, ``shoot_rays(..., max_bounces=K)``).  ``ValueError`` when ``R * n * F`` complex entries
     do not fit in the free device memory, before any kernel runs.  A device-resident fan is processed where it is and stays
     device resident."""
@@ -87,14 +89,21 @@ def transfer_function(rays, receiver_depths, env, frequencies, range_indices=Non
     f.to_device(device)
     import torch
     _check_fits(f, R, n, F, "transfer function", "entries")
-    offsets, tube, w, T, I, qa, col = _arrival_terms(f, cols, profile, boundary, counts)
+    lag = _lag_spec(bottom_loss)
+    offsets, tube, w, T, I, qa, col, *phi = _arrival_terms(f, cols, profile, boundary, counts, lag)
     La = None
     if alpha is not None:
         La = _arrival_lengths(f, col, tube, w) if len(tube) else torch.zeros(1, dtype=torch.float64, device=f.dev)
     tred = f.upload(np.tile(reduce, R))
     re, im = (torch.empty((R, n, F), dtype=torch.float64, device=f.dev) for _ in range(2))
-    _lib.spectrum_device(f.env.device, offsets.data_ptr(), R * n, T.data_ptr(), I.data_ptr(), qa.data_ptr(),
-                         0 if La is None else La.data_ptr(), tred.data_ptr(), freq, alpha, re.data_ptr(), im.data_ptr(), f.stream)
+    if lag is None:
+        _lib.spectrum_device(f.env.device, offsets.data_ptr(), R * n, T.data_ptr(), I.data_ptr(), qa.data_ptr(),
+                             0 if La is None else La.data_ptr(), tred.data_ptr(), freq, alpha, re.data_ptr(), im.data_ptr(),
+                             f.stream)
+    else:
+        _lib.spectrum_phi_device(f.env.device, offsets.data_ptr(), R * n, T.data_ptr(), I.data_ptr(), qa.data_ptr(),
+                                 phi[0].data_ptr(), 0 if La is None else La.data_ptr(), tred.data_ptr(), freq, alpha,
+                                 re.data_ptr(), im.data_ptr(), f.stream)
     return _to_host(f, cols, re, im)
 
 

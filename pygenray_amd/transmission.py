@@ -12,6 +12,7 @@ from . import _lib
 from .environment import _mirror_envi_arrays, _unpack_envi
 from .host_physics import bilinear_interp, linear_interp
 from .launch_rays import _device_env, _initial_slowness
+from .reflection import BottomReflection
 
 _NO_FE_MSG = ("Flat earth transformation has not been applied. Set `flat_earth_transform=True` "
               "when creating the OceanEnvironment2D object.")
@@ -58,7 +59,11 @@ def _loss_table(loss, name):
     """A boundary loss as the public functions take it -> (grazing-angle nodes in degrees or None, dB per bounce): None (no
     loss: 0.0 dB), a scalar in dB per bounce, or a pair ``(grazing_deg, dB)`` of equal-length 1-D sequences, the angles
     strictly ascending (linear between the nodes, held at the end values outside them).  Everything that can be refused
-    without a GPU is refused here."""
+    without a GPU is refused here.  A ``BottomReflection`` (the bottom only) stands for its ``.loss`` pair."""
+    if isinstance(loss, BottomReflection):
+        if name != "bottom_loss":
+            raise ValueError(f"{name}: a BottomReflection describes the bottom; pass it as bottom_loss")
+        loss = loss.loss
     if loss is None:
         return None, np.zeros(1)
     if isinstance(loss, (tuple, list)) and len(loss) == 2 and np.ndim(loss[0]) == 1:
@@ -87,6 +92,15 @@ def _boundary_spec(rays, bottom_loss, surface_loss):
     if not rays._has_bounce_log():
         raise ValueError("boundary loss needs a fan traced with a bounce log: shoot_rays(..., max_bounces=K)")
     return spec
+
+
+def _lag_spec(bottom_loss):
+    """None for every ``bottom_loss`` but a ``BottomReflection``; for one, the tables the boundary post-pass accumulates the
+    bottom's lag in cycles from: its ``.lag`` pair in the bottom's slot (one node: a constant) and 0.0 for the surface"""
+    if not isinstance(bottom_loss, BottomReflection):
+        return None
+    g, v = bottom_loss.lag
+    return ((None if len(g) == 1 else np.ascontiguousarray(g)), np.ascontiguousarray(v)), (None, np.zeros(1))
 
 
 def _ptr(t):
@@ -231,13 +245,13 @@ class _FanFrame(_TracedFan):
     def run(self, entry, *args):
         """Tube entry `entry` on the fan, with p0, the arguments after it and the stream: ``FanHandle.<entry>`` on a
         device-resident fan, else ``_lib.<entry>_device`` on the host fan's trajectories (ts only for ``arrivals`` and
-        ``pressure``)."""
+        ``pressure`` / ``pressure_phi``)."""
         args = (self.d_p0.data_ptr(),) + args + (self.stream,)
         # (the arrival counts have no weighted twin: finite weights leave the tubes counted as they are)
         kw = {"weights": self.d_W.data_ptr()} if self.d_W is not None and entry != "arrival_counts" else {}
         if self.handle is not None:
             return getattr(self.handle, entry)(*args, **kw)
-        fan = [self._host_fan(k) for k in (("ts", "zs", "ps") if entry in ("arrivals", "pressure") else ("zs", "ps"))]
+        fan = [self._host_fan(k) for k in (("ts", "zs", "ps") if entry in ("arrivals", "pressure", "pressure_phi") else ("zs", "ps"))]
         getattr(_lib, entry + "_device")(self.env, *fan, len(self.rays), len(self.x), self._host_fan("xf"), *args, **kw)
 
     def image(self):

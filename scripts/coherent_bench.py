@@ -3,7 +3,10 @@
 transmission_loss and -- unless --tl-only -- pressure_field (its caustic scan and bounce counts included).
 Meant to run under `rocprofv3 --kernel-trace --stats -- python scripts/coherent_bench.py ...`, one process per tree, so that
 each tree's kernels land in their own stats files; prints the wall clock of each call.
---root <checkout> --tl-only: measure that checkout's package (the parent commit's) with the same script."""
+--root <checkout> --tl-only: measure that checkout's package (the parent commit's) with the same script.
+--halfspace: also pressure_field over a sand-like fluid half-space, once with its magnitude alone
+(bottom_loss=<its .loss pair>: pgr_coh_sum with weights, one boundary post-pass) and once complex (bottom_loss=<the
+BottomReflection>: pgr_coh_sum_phi, the post-pass run once more for the lags), in the same process as the rigid call."""
 import argparse
 import json
 import os
@@ -13,6 +16,7 @@ import time
 ap = argparse.ArgumentParser()
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument("--tl-only", action="store_true", help="transmission_loss alone (a tree without pressure_field)")
+ap.add_argument("--halfspace", action="store_true", help="also pressure_field with bottom_loss=fluid_halfspace(1700, 1800, 0.5)")
 ap.add_argument("--rays", type=int, default=100_000)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--frequency", type=float, default=75.0)
@@ -40,6 +44,12 @@ depths = np.linspace(0.0, 5000.0, 1000)
 calls = {"transmission_loss": lambda: pr.transmission_loss(fan, depths, env, flatearth=False, intensity=True)}
 if not args.tl_only:
     calls["pressure_field"] = lambda: pr.pressure_field(fan, depths, env, args.frequency, flatearth=False)
+if args.halfspace:
+    sand = pr.fluid_halfspace(1700.0, 1800.0, 0.5)
+    calls["pressure_field_bottom_loss"] = lambda: pr.pressure_field(fan, depths, env, args.frequency, flatearth=False,
+                                                                    bottom_loss=sand.loss)
+    calls["pressure_field_halfspace"] = lambda: pr.pressure_field(fan, depths, env, args.frequency, flatearth=False,
+                                                                  bottom_loss=sand)
 wall = {k: [] for k in calls}
 for rep in range(args.reps + 1):
     for k, f in calls.items():

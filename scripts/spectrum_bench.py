@@ -5,7 +5,8 @@ and one exp per term more).  After a warm-up call, REPS calls of transfer_functi
 count / scan / emit, with --thorp the path length, and the sum itself).
 Meant to run under `rocprofv3 --kernel-trace --stats -- python scripts/spectrum_bench.py [--thorp]`, in a run of its own
 without counters, so that the kernels of the calls land in the stats files; without the profiler it prints the wall clock of
-each call."""
+each call.  --halfspace: every round also calls transfer_function with
+bottom_loss=fluid_halfspace(1700, 1800, 0.5) (pgr_spec_sum_phi), in the same process as the rigid call (pgr_spec_sum)."""
 import argparse
 import json
 import os
@@ -21,6 +22,7 @@ ap.add_argument("--frequencies", type=int, default=4096)
 ap.add_argument("--centre", type=float, default=75.0)
 ap.add_argument("--half-band", type=float, default=20.0)
 ap.add_argument("--thorp", action="store_true")
+ap.add_argument("--halfspace", action="store_true")
 args = ap.parse_args()
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np  # noqa: E402
@@ -41,16 +43,22 @@ cols = np.linspace(S // args.columns, S - 1, args.columns).astype(int)
 tred = np.asarray(fan.rs[0])[cols] / 1500.0
 freq = np.linspace(args.centre - args.half_band, args.centre + args.half_band, args.frequencies)
 kw = dict(absorption=pr.thorp_absorption) if args.thorp else {}
-wall, lit = [], None
+variants = {"rigid": {}}
+if args.halfspace:
+    variants["halfspace"] = dict(bottom_loss=pr.fluid_halfspace(1700.0, 1800.0, 0.5))
+walls, lit = {k: [] for k in variants}, None
 for rep in range(args.reps + 1):
-    torch.cuda.synchronize()
-    t = time.perf_counter()
-    H = pr.transfer_function(fan, depths, env, freq, range_indices=cols, t_reduce=tred, flatearth=False, **kw)
-    torch.cuda.synchronize()
-    if rep:
-        wall.append(1e3 * (time.perf_counter() - t))
-    lit = float((np.abs(H) > 0).mean())
-    del H
+    for name, extra in variants.items():
+        torch.cuda.synchronize()
+        t = time.perf_counter()
+        H = pr.transfer_function(fan, depths, env, freq, range_indices=cols, t_reduce=tred, flatearth=False, **kw, **extra)
+        torch.cuda.synchronize()
+        if rep:
+            walls[name].append(1e3 * (time.perf_counter() - t))
+        if name == "rigid":
+            lit = float((np.abs(H) > 0).mean())
+        del H
+wall = walls["rigid"]
 assert fan.device_resident
 a = pr.arrivals(fan, depths, env, flatearth=False, range_indices=cols)
 nb, ns = fan.bounce_counts(cols)
@@ -61,4 +69,6 @@ print(json.dumps({"rays": len(fan), "depths": args.depths, "columns": [int(c) fo
                   "bytes_written": args.depths * args.columns * args.frequencies * 16, "arrivals": len(a),
                   "arrivals_that_add": adding, "terms_per_call": adding * args.frequencies, "fraction_of_entries_lit": lit,
                   "build": _lib.build_info(), "device_code_sha256": _lib.device_code_sha256(), "wall_ms": wall,
-                  "wall_ms_median": float(np.median(wall))}))
+                  "wall_ms_median": float(np.median(wall)),
+                  **({"halfspace_wall_ms": walls["halfspace"], "halfspace_wall_ms_median": float(np.median(walls["halfspace"]))}
+                     if args.halfspace else {})}))
