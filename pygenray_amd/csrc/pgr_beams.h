@@ -105,8 +105,8 @@ __device__ __forceinline__ void gb_chunk_tubes(const GbArgs& g, const Ctx<false,
     const double q1 = __shfl_down(y.q0, 1), q2 = __shfl_down(y.q0, 2);
     double A = 0.0;
     if (t < GB_TUBES && k + 1 < g.M && g1 == g1 && g2 == g2) {
-        const double E = fdiv(0.5 * (g1 + g2) * fabs(q2 - q1), r);
-        A = fdiv(E, sig * GB_SQRT_2PI);
+        const double E = fdiv_inf(0.5 * (g1 + g2) * fabs(q2 - q1), r);          // (g W can be infinite, as in tl_chunk_tubes)
+        A = fdiv_inf(E, sig * GB_SQRT_2PI);
     } else {
         mid = NAN;                                   // every test of a NaN centre fails: the tube adds nothing
     }

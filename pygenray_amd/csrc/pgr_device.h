@@ -148,6 +148,13 @@ __device__ __forceinline__ double fdiv(double a, double b)
     double r = fma(-q, b, a);
     return fma(r, y, q);
 }
+// fdiv() where the numerator may be infinite (a tube whose weight 10^(-A/10) overflowed): a / b = a for 0 < b < inf, as
+// IEEE 754 has it -- fdiv's own correction step forms inf - inf there and gives NaN
+__device__ __forceinline__ double fdiv_inf(double a, double b)
+{
+    const double q = fdiv(a, b);
+    return (fabs(a) == INFINITY && b > 0.0 && b < INFINITY) ? a : q;
+}
 // 1/b to ~2e-15 (v_rcp_f64 + one Newton step): a SEED for fdiv_y, whose correction step squares
 // the seed's error -- exactly what fdiv() itself does
 __device__ __forceinline__ double frcp_seed(double b)

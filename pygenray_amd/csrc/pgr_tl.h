@@ -196,7 +196,7 @@ __device__ __forceinline__ void tl_chunk_tubes(const TlArgs& a, const Ctx<false,
     if (t < TL_TUBES && m + 1 < a.M && g == g && g1 == g1 && dz != dz1) {
         lo = fmin(dz, dz1);
         hi = fmax(dz, dz1);
-        I = fdiv(0.5 * (g + g1) * fabs(q1 - q0), r * fabs(dz1 - dz));
+        I = fdiv_inf(0.5 * (g + g1) * fabs(q1 - q0), r * fabs(dz1 - dz));   // (g W can be infinite: a weight that overflowed)
     }
     __syncthreads();                               // (the previous chunk's tubes have been read)
     L.lo[t] = lo;

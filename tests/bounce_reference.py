@@ -38,9 +38,9 @@ def grazing(x, p, kind, cin, rin, zin, br, bd, beta):
     return (abs(theta - float(table_at(x, *beta))) if kind else abs(theta)), pc
 
 
-def event_loss(bx, bp, bk, cin, rin, zin, br, bd, bottom, surface, beta, psign=-1.0):
+def event_loss_one_by_one(bx, bp, bk, cin, rin, zin, br, bd, bottom, surface, beta, psign=-1.0):
     """loss_e of every slot of a log (any shape): NaN where bx or bp is NaN or |p c| > 1; 0.0 in the slots without an event.
-    bottom / surface / beta: (nodes or None, values) tables."""
+    bottom / surface / beta: (nodes or None, values) tables.  The definition, one event at a time through grazing()."""
     bx, bp, bk = np.asarray(bx, dtype=float), np.asarray(bp, dtype=float), np.asarray(bk)
     out = np.zeros(bx.shape)
     for idx in np.ndindex(bx.shape):
@@ -49,6 +49,26 @@ def event_loss(bx, bp, bk, cin, rin, zin, br, bd, bottom, surface, beta, psign=-
             continue
         phi = grazing(bx[idx], psign * bp[idx], kind, cin, rin, zin, br, bd, beta)[0]
         out[idx] = float(table_at(phi, *(bottom if kind else surface))) if phi == phi else np.nan
+    return out
+
+
+def event_loss(bx, bp, bk, cin, rin, zin, br, bd, bottom, surface, beta, psign=-1.0):
+    """event_loss_one_by_one over all events at once: the same operations on every event, in the same order, so the same
+    bits (tests/test_bounce_log_host.py compares the two); one call of the oracle's asin for the whole log."""
+    bx, bp, bk = np.asarray(bx, dtype=float), np.asarray(bp, dtype=float), np.asarray(bk)
+    out = np.zeros(bx.shape)
+    live = bk >= 0
+    if not live.any():
+        return out
+    x, p, kind = bx[live], psign * bp[live], bk[live] > 0
+    with np.errstate(invalid="ignore"):
+        d = np.where(kind, bottom_at(x, br, bd), 0.0)
+        pc = p * tlr.bilinear(x, d, rin, zin, cin)
+        ok = (x == x) & (p == p) & (np.abs(pc) <= 1.0)
+        theta = np.full(x.shape, np.nan)
+        theta[ok] = oracle.math_fn("asin", pc[ok]) * DEG
+        phi = np.where(kind, np.abs(theta - table_at(x, *beta)), np.abs(theta))
+        out[live] = np.where(kind, table_at(phi, *bottom), table_at(phi, *surface))
     return out
 
 
@@ -100,10 +120,13 @@ def segments_by_slice_assignment(x, starts, x_end):
     return owner
 
 
-def trace_bounces(arrs, y0, x0, x1, max_rows=60000):
+def trace_bounces(arrs, y0, x0, x1, max_rows=60000, rtol=1e-9, terminate_backwards=True):
     """the bounces of one ray from the oracle's step trace (correctly rounded libm): the first row of every segment k >= 1
-    holds the bounce's range and the reflected state -> (bx, bp ODE sign, bk) arrays; bk from the boundary the depth sits on"""
-    rows = oracle.trace_ray(*arrs, y0, x0, x1, math=oracle.MATH_CR, max_rows=max_rows)
+    holds the bounce's range and the reflected state -> (bx, bp ODE sign, bk) arrays; bk from the boundary the depth sits on.
+    rtol / terminate_backwards: the shot's own, handed to oracle.trace_ray; max_rows: the step attempts the trace may hold
+    (asserted not to be reached)"""
+    rows = oracle.trace_ray(*arrs, y0, x0, x1, rtol=rtol, terminate_backwards=terminate_backwards, math=oracle.MATH_CR,
+                            max_rows=max_rows)
     assert 0 < len(rows) < max_rows
     first = np.flatnonzero(np.diff(rows[:, 11]) > 0) + 1
     bx, bz, bp = rows[first, 0], rows[first, 3], rows[first, 4]

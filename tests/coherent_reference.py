@@ -95,6 +95,14 @@ def tube_phase(kappa, nb, ns):
 
 # ---- the coherent tube sum --------------------------------------------------------------------------------------------------
 
+def as_complex(re, im):
+    """re + i im with each part's own bits: `re + 1j * im` multiplies im by (0 + 1j), and 0 * inf puts a NaN into the real part
+    of a sum that is infinite in the imaginary one only"""
+    out = np.empty(np.shape(re), dtype=np.complex128)
+    out.real, out.imag = re, im
+    return out
+
+
 def phase_cycles(T, q, f):
     """t of the definition: f T - q / 4 brought to [-0.5, 0.5] cycles in the kernel's steps"""
     y = f * T
@@ -233,4 +241,4 @@ def fan_pressure(rays, depths, environment, f, flatearth=True, W=None, nb=None, 
     if q is None:
         q = tube_phase(caustic_index(-np.asarray(rays.zs), nb, ns), nb, ns)
     re, im = tube_pressure(rays.zs, rays.ps, rays.ts, x, p0, depths, cin, rin, zin, W, q, f)
-    return re + 1j * im
+    return as_complex(re, im)

@@ -13,6 +13,9 @@ What the definition of the tube products says (DESIGN.md sections 8-10), restate
   WGS-84 radius at the environment's latitude;
 - a backwards fan (save ranges decreasing) was traced in the mirrored frame x' = -x: ranges negated and reversed, table
   rows reversed, the bathymetry likewise; its save ranges are -x;
+- the bottom slope at a bounce comes from the bathymetry as the user gave it, flat-earth mapped or not:
+  ``degrees(arctan(np.gradient(bathymetry, its ranges)))`` on the bathymetry's ranges; negated and reversed in the mirrored
+  frame;
 - the bottom at a save range is the linear interpolation of the bathymetry (cell = searchsorted - 1, clamped; weights not
   clamped);
 - ``p0 = sin(radians(theta)) / c_source``, ``c_source`` the bilinear look-up at (the traced frame's first save range, the
@@ -78,6 +81,20 @@ def traced_frame(environment, x, flatearth):
         cin, rin, bd, br = cin[flip], -rin[flip], bd[flip_b], -br[flip_b]
         x = -x
     return x, np.ascontiguousarray(cin), rin, zin, bd, br
+
+
+def bottom_slope(environment, x):
+    """The bottom slope of the frame a fan with save ranges x (S,) was traced in -> (its ranges, degrees): the slope of the
+    UNTRANSFORMED bathymetry, degrees(arctan(d depth / d range)) by np.gradient on the bathymetry's own range grid, whatever
+    ``flatearth`` is (the reference's quirk Q10); negated and reversed, with the ranges, for a backwards fan."""
+    x = np.array(x, dtype=float)
+    ba = environment.bathymetry
+    br = _coord(ba, "range")
+    beta = np.degrees(np.arctan(np.gradient(np.array(ba.values, dtype=float), br)))
+    if len(x) > 1 and x[-1] < x[0]:
+        flip = np.arange(len(br) - 1, -1, -1)
+        br, beta = -br[flip], -beta[flip]
+    return br, beta
 
 
 def bottom_at(xf, bd, br):

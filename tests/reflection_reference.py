@@ -137,7 +137,7 @@ def signal_sum(off, T, I, q, phi, tstart, f, rs, dt, n_times):
             E = gexp(-0.5 * np.where(keep, v, 0.0))
             re[g] = np.where(keep, re[g] + C[a][:, None] * E, re[g])
             im[g] = np.where(keep, im[g] + Sn[a][:, None] * E, im[g])
-    return re + 1j * im
+    return cref.as_complex(re, im)
 
 
 def cw_sum(off, T, I, q, phi, f):
@@ -180,7 +180,7 @@ def spectrum_sum(off, T, I, q, phi, L, tred, freq, alpha):
                 W = spref.amplitude_weight(np.asarray(alpha, dtype=float)[None, :], np.asarray(L, dtype=float)[a][:, None])
                 re[g] = re[g] + (amp[a][:, None] * cv) * W
                 im[g] = im[g] + (amp[a][:, None] * sv) * W
-    return re + 1j * im
+    return cref.as_complex(re, im)
 
 
 # ---- synthetic inputs of the GPU tests ----------------------------------------------------------------------------------------
@@ -227,7 +227,7 @@ def fan_pressure(rays, depths, environment, f, Phi, flatearth=True, W=None, nb=N
     x, cin, rin, zin, _, _, _, p0 = fan_frame(rays, environment, flatearth)
     q = cref.tube_phase(cref.caustic_index(-np.asarray(rays.zs), nb, ns), nb, ns)
     re, im = tube_pressure(rays.zs, rays.ps, rays.ts, x, p0, depths, cin, rin, zin, W, q, f, Phi)
-    return re + 1j * im
+    return cref.as_complex(re, im)
 
 
 def fan_arrivals(rays, depths, environment, cols, Phi, flatearth=True, nb=None, ns=None):

@@ -58,7 +58,7 @@ def signal_sum(off, T, I, q, tstart, f, rs, dt, n_times):
             E = gexp(-0.5 * np.where(keep, v, 0.0))
             re[g] = np.where(keep, re[g] + C[a][:, None] * E, re[g])
             im[g] = np.where(keep, im[g] + Sn[a][:, None] * E, im[g])
-    return re + 1j * im
+    return cref.as_complex(re, im)
 
 
 def cw_sum(off, T, I, q, f):

@@ -59,7 +59,7 @@ def spectrum_sum(off, T, I, q, L, tred, freq, alpha):
                 W = amplitude_weight(np.asarray(alpha, dtype=float)[None, :], np.asarray(L, dtype=float)[a][:, None])
                 re[g] = re[g] + (amp[a][:, None] * cv) * W
                 im[g] = im[g] + (amp[a][:, None] * sv) * W
-    return re + 1j * im
+    return cref.as_complex(re, im)
 
 
 def waveform(H_of, source, dt, carrier, t0, n_fft, n_times=None):

@@ -401,10 +401,16 @@ def test_sample_assignment_is_the_oracle_segments(lib, small_cases, pr):  # noqa
 
 
 def _traced_beta(env, xf, flatearth, backwards):
+    """the bottom slope of the traced frame from frame_independent.py, which shares no code with the package -- and, asserted
+    here, the very arrays the package's own frame helper hands the post-pass"""
     from pygenray_amd.environment import _unpack_envi
+    br, ang = fi.bottom_slope(env, -xf if backwards else xf)
     arrs = _unpack_envi(env, flatearth=flatearth)
-    br, ang = np.asarray(arrs[5], dtype=float), np.asarray(arrs[6], dtype=float)
-    return (-br[::-1], -ang[::-1]) if backwards else (br, ang)
+    own_br, own_ang = np.asarray(arrs[5], dtype=float), np.asarray(arrs[6], dtype=float)
+    if backwards:
+        own_br, own_ang = -own_br[::-1], -own_ang[::-1]
+    assert _same(br, own_br) and _same(ang, own_ang)
+    return br, ang
 
 
 def wall_env(pr):  # noqa: F811

@@ -41,6 +41,34 @@ def test_argmin_rule_is_the_reference_slice_assignment(S):
         assert np.array_equal(nb[0], seg) and not ns.any()
 
 
+def test_event_loss_over_all_events_at_once_is_the_loss_one_event_at_a_time():
+    """bounce_reference.event_loss (one call of the oracle's asin for the whole log) against the per-event form it restates,
+    bit for bit: a range-dependent table over a sloping floor, both signs of p, both boundaries, tables with nodes inside
+    (0, 90) and constants, empty slots, NaN bx / bp, |p c| = 1 and > 1, events outside the tables' ranges"""
+    rng = np.random.default_rng(14)
+    rin, zin = np.sort(rng.uniform(-40e3, 90e3, 9)), np.linspace(0.0, 5000.0, 41) ** 1.1
+    cin = 1480.0 + 0.016 * zin[None, :] + 6.0 * np.sin(rin / 2e4)[:, None]
+    br = np.sort(rng.uniform(-40e3, 90e3, 7))
+    bd = 3000.0 + 400.0 * np.sin(br / 3e4)
+    beta = (br, np.degrees(np.arctan(np.gradient(bd, br))))
+    M, K = 37, 6
+    bx = rng.uniform(-45e3, 95e3, (M, K))
+    bp = np.sin(np.radians(rng.uniform(-89.0, 89.0, (M, K)))) / 1500.0
+    bk = rng.integers(-1, 2, (M, K)).astype(np.int8)
+    bp[3, 1], bx[5, 2], bp[7, 0], bp[8, 0] = np.nan, np.nan, 1.0 / 1400.0, -1.0 / 1400.0
+    bk[[3, 5, 7, 8], [1, 2, 0, 0]] = [1, 0, 1, 0]
+    c = bref.tlr.bilinear(bx[9, 0], 0.0, rin, zin, cin)
+    bp[9, 0], bk[9, 0] = 1.0 / c, 0
+    tables = [((np.array([2.0, 11.0, 35.0, 80.0]), np.array([0.5, 3.0, 1.0, 9.0])), (None, np.array([0.25])), beta),
+              ((None, np.array([1.5])), (np.array([1.0, 30.0]), np.array([0.0, 2.0])), (None, np.zeros(1)))]
+    for bottom, surface, slope in tables:
+        for psign in (-1.0, 1.0):
+            a = bref.event_loss(bx, bp, bk, cin, rin, zin, br, bd, bottom, surface, slope, psign)
+            b = bref.event_loss_one_by_one(bx, bp, bk, cin, rin, zin, br, bd, bottom, surface, slope, psign)
+            assert np.array_equal(a, b, equal_nan=True)
+            assert np.isnan(a).sum() >= 3 and (a[bk < 0] == 0).all() and (a[~np.isnan(a)] > 0).sum() > 50
+
+
 def _host_fan(M=5, S=9, K=4, backwards=False):
     x = np.linspace(40e3, 0.0, S) if backwards else np.linspace(0.0, 40e3, S)
     z = np.zeros((M, S))

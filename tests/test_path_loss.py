@@ -394,6 +394,35 @@ def test_weighted_kernels_bit_identical_on_the_synthetic_seam_cases(pr, syn_env,
     assert all(_same(none[k], same[k]) for k in same)
 
 
+def test_weights_that_overflowed_give_the_ieee_quotient(pr, syn_env):
+    """A path integral that comes out hugely negative (a sample extrapolated far out of the sound-speed table, where the
+    bilinear c is negative) makes W = 10^(-A / 10) infinite: the tube's term is then inf / finite = inf, not the NaN the
+    refined-reciprocal division forms by itself -- in TL, the arrivals and the beams, next to a neighbour of weight 0"""
+    env, cin = syn_env
+    M, S, R = 130, 4, 40
+    z, p, x, p0, depths = synthetic_fan(M, S, R, seed=77, cin=cin)
+    rng = np.random.default_rng(5)
+    t = np.cumsum(rng.uniform(0.2, 1.5, (S, M)), axis=0)
+    W = synthetic_weights(M, S, 9)
+    W[:, 10:M:23] = np.inf
+    W[:, 11:M:23] = 0.0
+    W[1, 64] = W[1, 65] = np.inf
+    ref = pref.tube_intensity(z.T, p.T, x, p0, depths, cin, SYN_R, SYN_Z, W.T)
+    assert np.isinf(ref).any()
+    I = _device_intensity_w(env, z, p, x, p0, depths, W)
+    assert _same(I, ref), np.argwhere(~((I == ref) | (np.isnan(I) & np.isnan(ref))))[:5]
+    bottom = np.linspace(4700.0, 5150.0, S)
+    ref = pref.beam_intensity(z.T, p.T, x, p0, depths, cin, SYN_R, SYN_Z, bottom, 25.0, W.T)
+    assert np.isinf(ref).any()
+    assert _same(_device_intensity_w(env, z, p, x, p0, depths, W, beams=(bottom, 25.0)), ref)
+    cols = list(range(S))
+    got, _ = _device_arrivals_w(env, t, z, p, x, p0, depths, cols, W)
+    ref = pref.tube_arrivals(z.T, p.T, t.T, x, p0, depths, cols, cin, SYN_R, SYN_Z, W.T)
+    assert np.array_equal(got["offsets"], ref["offsets"]) and np.isinf(ref["I"]).any()
+    for k in ("tube", "w", "T", "p", "I"):
+        assert _same(got[k], ref[k]), k
+
+
 @pytest.mark.parametrize("which, resident, flatearth", [("munk", True, False), ("sloping", True, False), ("sloping", False, False),
                                                         ("default", True, True)])
 def test_weighted_fan_products_bit_identical_to_the_restatements(pr, which, resident, flatearth):
