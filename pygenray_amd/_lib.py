@@ -123,6 +123,13 @@ try:
         REFLECTION_PROTOTYPES = parse_header(_f.read())[0]
 except OSError as _e:
     raise PgrError(f"{REFLECTION_HEADER}: the C ABI header cannot be read ({_e})") from None
+# ... and the coherent Gaussian-beam pressure with wavefront curvature, likewise
+BEAM_COHERENT_HEADER = os.path.join(_HERE, "..", "include", "pgr_beam_coherent.h")
+try:
+    with open(BEAM_COHERENT_HEADER) as _f:
+        BEAM_COHERENT_PROTOTYPES = parse_header(_f.read())[0]
+except OSError as _e:
+    raise PgrError(f"{BEAM_COHERENT_HEADER}: the C ABI header cannot be read ({_e})") from None
 globals().update(_CONSTANTS)   # PGR_TERMINATE_BACKWARDS, PGR_SAMPLE_MAJOR, ... PGR_OPT_D2H_REGISTER
 
 _REBUILD = "`python -c 'import __graft_entry__ as g; g.build()'`"
@@ -209,7 +216,7 @@ def build(force=False, verbose=False, out=None, extra_flags=()):
     src = os.path.join(CSRC, "pgr_hip.hip")
     hdr = os.path.join(_HERE, "..", "include", "pgr.h")
     # (one translation unit: pgr_hip.hip includes every csrc/*.h -- device building blocks, the fan kernel, the host side in pieces)
-    deps = [src, hdr, COHERENT_HEADER, SIGNAL_HEADER, SPECTRUM_HEADER, REFLECTION_HEADER, os.path.join(_HERE, "_isa_layout.py")] + sorted(
+    deps = [src, hdr, COHERENT_HEADER, SIGNAL_HEADER, SPECTRUM_HEADER, REFLECTION_HEADER, BEAM_COHERENT_HEADER, os.path.join(_HERE, "_isa_layout.py")] + sorted(
         os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h"))
     if not force and os.path.exists(LIB_PATH):
         if os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(d) for d in deps):
@@ -274,11 +281,11 @@ def load():
             "). pygenray_amd has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**PROTOTYPES, **COHERENT_PROTOTYPES, **SIGNAL_PROTOTYPES, **SPECTRUM_PROTOTYPES,
-                                      **REFLECTION_PROTOTYPES}.items():
+                                      **REFLECTION_PROTOTYPES, **BEAM_COHERENT_PROTOTYPES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError:
-            raise PgrError(f"{LIB_PATH} does not export {name}, which include/pgr.h declares (itself or through pgr_coherent.h / pgr_signal.h / pgr_spectrum.h / pgr_reflection.h): the library is older than "
+            raise PgrError(f"{LIB_PATH} does not export {name}, which include/pgr.h declares (itself or through pgr_coherent.h / pgr_signal.h / pgr_spectrum.h / pgr_reflection.h / pgr_beam_coherent.h): the library is older than "
                            f"the header. Rebuild it: {_REBUILD}.") from None
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -636,6 +643,15 @@ class FanHandle:
         check(load().pgr_fan_pressure_phi(self._h, p0_ptr, weights or None, q_ptr or None, phi_ptr or None, float(frequency),
                                           depths_ptr, int(n_depths), re_ptr, im_ptr, stream))
 
+    def beam_pressure(self, p0_ptr, q_ptr, frequency, bottom_ptr, depths_ptr, n_depths, min_width, curvature, re_ptr, im_ptr,
+                      stream=0, weights=0):
+        """pgr_fan_beam_pressure_w on raw device pointers (ints): re / im [n_depths][S] = the coherent sum of this fan's
+        Gaussian beams at the receiver depths; q and `weights` as in ``pressure``, bottom and min_width as in
+        ``beam_intensity``, `curvature` false for the plain geometric beam (include/pgr_beam_coherent.h)."""
+        check(load().pgr_fan_beam_pressure_w(self._h, p0_ptr, weights or None, q_ptr or None, float(frequency), bottom_ptr,
+                                             depths_ptr, int(n_depths), float(min_width), int(bool(curvature)), re_ptr, im_ptr,
+                                             stream))
+
     def close(self):
         if getattr(self, "_h", None):
             load().pgr_fan_destroy(self._h)
@@ -835,6 +851,15 @@ def pressure_phi_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_p
     check(load().pgr_pressure_device_phi(env._h, t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr,
                                          weights or None, q_ptr or None, phi_ptr or None, float(frequency), depths_ptr,
                                          int(n_depths), re_ptr, im_ptr, stream))
+
+
+def beam_pressure_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, q_ptr, frequency, bottom_ptr, depths_ptr,
+                         n_depths, min_width, curvature, re_ptr, im_ptr, stream=0, weights=0):
+    """pgr_beam_pressure_device_w on raw device pointers (ints; q / weights 0: absent): the coherent Gaussian-beam sum of caller
+    buffers T / z / p [n_samples][n_rays] (stored sign convention) on `env` (an EnvHandle); see include/pgr_beam_coherent.h."""
+    check(load().pgr_beam_pressure_device_w(env._h, t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr,
+                                            weights or None, q_ptr or None, float(frequency), bottom_ptr, depths_ptr,
+                                            int(n_depths), float(min_width), int(bool(curvature)), re_ptr, im_ptr, stream))
 
 
 def signal_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, tstart_ptr, frequency, inv_sigma, dt, n_times, re_ptr,

@@ -1,13 +1,15 @@
-"""Coherent ray-tube field of a fan: ``caustic_index``, ``pressure_field``, ``coherent_transmission_loss`` (DESIGN.md,
-"Coherent ray-tube pressure").
+"""Coherent field of a fan: ``caustic_index``, ``pressure_field``, ``coherent_transmission_loss`` ("Coherent
+ray-tube pressure") and ``beam_pressure_field``, ``coherent_beam_transmission_loss``, the same tubes spread as geometric
+Gaussian beams with the wavefront curvature in their phase ("Coherent Gaussian-beam pressure").
 
-No reference counterpart: pygenray gives back rays, not amplitudes.  The caustic index of every tube and the coherent sum of
-the tubes run in HIP (csrc/pgr_phase.h) on the fan's trajectories where they already are -- in HBM for a device-resident
+No reference counterpart: pygenray gives back rays, not amplitudes.  The caustic index of every tube and the coherent sums
+run in HIP (csrc/pgr_phase.h, csrc/pgr_beam_phase.h) on the fan's trajectories where they already are -- in HBM for a device-resident
 fan, uploaded through torch for a host fan.  There is no CPU path.
 """
 import numpy as np
 
 from . import _lib
+from .reflection import BottomReflection
 from .transmission import (_FanFrame, _TracedFan, _absorption_profile, _boundary_spec, _check_flatearth, _lag_spec,
                            _loss_table, _ptr, _save_grid)
 
@@ -152,4 +154,67 @@ def coherent_transmission_loss(rays, receiver_depths, env, frequency, absorption
         return -20.0 * np.log10(np.abs(p))
 
 
-__all__ = ["caustic_index", "pressure_field", "coherent_transmission_loss"]
+def beam_pressure_field(rays, receiver_depths, env, frequency, min_width=10.0, curvature=True, absorption=None,
+                        bottom_loss=None, surface_loss=None, flatearth=True, device=0):
+    """Coherent Gaussian-beam pressure of ``rays`` (a ``RayFan`` from ``shoot_rays``) at ``receiver_depths`` (metres, positive
+    down, strictly ascending) on the fan's save ranges, at ``frequency`` (Hz, finite, >= 0) -> complex128 ndarray
+    ``(len(receiver_depths), S)``, re 1 m: 0 where no beam reaches, NaN in the source's own column.  The ray tubes of
+    ``pressure_field``, each spread over depth as the geometric Gaussian beam of ``beam_transmission_loss`` -- the same centre
+    m_k, width sigma_k = max(the tube's and its neighbours' widths, ``min_width``), energy E_k and cut at 4 sigma_k -- and
+    carrying the tube's phase: the beam, its image in the pressure-release surface (a half cycle) and its image in the rigid
+    bottom each add
+
+        A'_k exp(-e^2 / (2 sigma_k^2)) exp(i (2 pi f (T_m + p_m e + kappa_k e^2 / 2) - (pi / 2) q)),
+        A'_k = sqrt(E_k D_k) / (sigma_k sqrt(2 pi)),   kappa_k = (p_k+1 - p_k) / (d_k+1 - d_k)
+
+    with e the receiver's offset from the beam's centre (mirrored with the image), T_m and p_m the means of the two rays'
+    travel time and vertical slowness dT/dz, D_k the tube's width and q = kappa + 2 n_surf ``pressure_field``'s phase index.
+    Beams D apart and sigma wide, in phase, sum to sqrt(E / D), the tube's amplitude, so away from caustics and boundaries
+    the field is ``pressure_field``'s; at a caustic, where D -> 0, A' -> 0 and the field stays bounded by the sum of the
+    beams' amplitudes, the receivers along both boundaries are reached by the images, and shadow edges are sigma wide.
+    ``curvature`` (default True): kappa_k, the wavefront's curvature across the tube, which keeps a beam much wider than its
+    tube (sigma_k = ``min_width``, about a wavelength) accurate; False gives the plain geometric beam, linear phase only.
+    kappa_k grows without bound at a caustic while A' -> 0 there.  A tube whose two rays have bounced a different number of
+    times adds nothing, as in ``pressure_field``.
+
+    ``absorption``, ``bottom_loss``, ``surface_loss``: the weights of ``transmission_loss``, exactly.  A ``BottomReflection``
+    as ``bottom_loss`` is refused with a ``ValueError``: the beam product does not yet apply a complex bottom phase, and its
+    magnitude alone would be wrong physics; pass its ``.loss`` pair for the loss without the phase.  The frame, the sound
+    speed and the bathymetry are ``beam_transmission_loss``'s.  A fan with bounces needs its bounce log
+    (``shoot_rays(..., max_bounces=K)``): ``ValueError`` otherwise.  A device-resident fan is processed where it is and stays
+    device resident."""
+    f0, w = float(frequency), float(min_width)
+    if not (np.isfinite(f0) and f0 >= 0):
+        raise ValueError("frequency must be finite and >= 0 Hz")
+    if not (np.isfinite(w) and w > 0):
+        raise ValueError("min_width must be finite and > 0")
+    if isinstance(bottom_loss, BottomReflection):
+        raise ValueError("beam_pressure_field does not yet apply a complex bottom phase: a BottomReflection as bottom_loss is "
+                         "refused (its magnitude alone would be wrong physics); pass bottom_loss=reflection.loss for the "
+                         "loss without the phase")
+    profile = None if absorption is None else _absorption_profile(absorption)
+    boundary = _boundary_spec(rays, bottom_loss, surface_loss)
+    f = _FanFrame(rays, receiver_depths, env, flatearth, "beam_pressure_field")
+    counts = _needs_counts(rays)
+    f.to_device(device).absorb(profile, boundary, counts=counts)      # (one run of the boundary loss: weights and counts)
+    import torch
+    q = _phase_index(f, counts)
+    re, im, d_b = f.image(), f.image(), f.upload(f.bottom())
+    f.run("beam_pressure", q.data_ptr(), f0, d_b.data_ptr(), f.d_depths.data_ptr(), len(f.depths), w, bool(curvature),
+          re.data_ptr(), im.data_ptr())
+    return torch.complex(re, im).cpu().numpy()
+
+
+def coherent_beam_transmission_loss(rays, receiver_depths, env, frequency, min_width=10.0, curvature=True, absorption=None,
+                                    bottom_loss=None, surface_loss=None, flatearth=True, device=0):
+    """Coherent Gaussian-beam transmission loss: ``-20 log10 |p|`` dB re 1 m of ``beam_pressure_field``, whose arguments it
+    takes (``+inf`` where no beam reaches or the paths cancel, NaN in the source's own column)."""
+    p = beam_pressure_field(rays, receiver_depths, env, frequency, min_width=min_width, curvature=curvature,
+                            absorption=absorption, bottom_loss=bottom_loss, surface_loss=surface_loss, flatearth=flatearth,
+                            device=device)
+    with np.errstate(divide="ignore"):
+        return -20.0 * np.log10(np.abs(p))
+
+
+__all__ = ["caustic_index", "pressure_field", "coherent_transmission_loss", "beam_pressure_field",
+           "coherent_beam_transmission_loss"]

@@ -6,7 +6,10 @@ each tree's kernels land in their own stats files; prints the wall clock of each
 --root <checkout> --tl-only: measure that checkout's package (the parent commit's) with the same script.
 --halfspace: also pressure_field over a sand-like fluid half-space, once with its magnitude alone
 (bottom_loss=<its .loss pair>: pgr_coh_sum with weights, one boundary post-pass) and once complex (bottom_loss=<the
-BottomReflection>: pgr_coh_sum_phi, the post-pass run once more for the lags), in the same process as the rigid call."""
+BottomReflection>: pgr_coh_sum_phi, the post-pass run once more for the lags), in the same process as the rigid call.
+--beams: also beam_transmission_loss (pgr_gb_sum) and beam_pressure_field (pgr_gbc_sum) at --min-width,
+in the same process, so that the three sums' kernels come from one run; a checkout without beam_pressure_field (--root <the
+parent's>) runs the other two."""
 import argparse
 import json
 import os
@@ -17,6 +20,8 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--root", default=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 ap.add_argument("--tl-only", action="store_true", help="transmission_loss alone (a tree without pressure_field)")
 ap.add_argument("--halfspace", action="store_true", help="also pressure_field with bottom_loss=fluid_halfspace(1700, 1800, 0.5)")
+ap.add_argument("--beams", action="store_true", help="also beam_transmission_loss and (where the tree has it) beam_pressure_field")
+ap.add_argument("--min-width", type=float, default=10.0)
 ap.add_argument("--rays", type=int, default=100_000)
 ap.add_argument("--reps", type=int, default=3)
 ap.add_argument("--frequency", type=float, default=75.0)
@@ -50,6 +55,12 @@ if args.halfspace:
                                                                     bottom_loss=sand.loss)
     calls["pressure_field_halfspace"] = lambda: pr.pressure_field(fan, depths, env, args.frequency, flatearth=False,
                                                                   bottom_loss=sand)
+if args.beams:
+    calls["beam_transmission_loss"] = lambda: pr.beam_transmission_loss(fan, depths, env, flatearth=False, intensity=True,
+                                                                        min_width=args.min_width)
+    if hasattr(pr, "beam_pressure_field"):
+        calls["beam_pressure_field"] = lambda: pr.beam_pressure_field(fan, depths, env, args.frequency, flatearth=False,
+                                                                      min_width=args.min_width)
 wall = {k: [] for k in calls}
 for rep in range(args.reps + 1):
     for k, f in calls.items():

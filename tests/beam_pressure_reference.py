@@ -1,0 +1,166 @@
+"""Test helpers for beam_pressure_field (not a product path): a plain NumPy restatement of DESIGN.md section 20, written from
+the definition in its operation order -- the tubes' centres and widths from beam_reference, the weighted g of path_reference,
+the library's exp (beam_reference.gexp) and cos / sin of 2 pi t (coherent_reference) -- and the set-ups shared by the CPU and
+GPU tests: Lloyd's mirror and the free field on exact straight rays, with the values measured on them."""
+import numpy as np
+
+import beam_reference as bref
+import coherent_reference as cref
+import path_reference as pref
+
+
+def beam_pressure(zs, ps, ts, x, p0, depths, cin, rin, zin, bottom, w_min, W, q, f, curvature=True, detail=False):
+    """The definition, restated: zs / ps / ts (M, S) stored convention (depth d = -z, slowness along increasing depth -p),
+    x (S,) save ranges in the frame of the tables, p0 (M,), bottom (S,), weights W (M, S) or None, phase index q (M, S)
+    integers or None, frequency f -> (re, im), each (len(depths), S).  Per column the tubes in increasing k, per tube the
+    centres m, -m, 2 b - m, every kept term added to its receiver's two sums one at a time.  With `detail` also, per receiver,
+    the sum of a in the same order and the sum of A' over the kept terms."""
+    zs, ps, ts, x, depths, bottom = (np.asarray(a, dtype=float) for a in (zs, ps, ts, x, depths, bottom))
+    d, pd = -zs, -ps
+    M, S = d.shape
+    R = len(depths)
+    g = pref.weighted_g(zs, ps, x, cin, rin, zin, W)
+    _, mid, sigma, _, _, r = bref._tubes(zs, ps, x, p0, cin, rin, zin, w_min)      # centres and widths: section 10's
+    order = np.argsort(depths, kind="stable")
+    ds = depths[order]
+    re, im, asum, Asum = (np.zeros((R, S)) for _ in range(4))
+    with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
+        valid = ~np.isnan(g[:-1]) & ~np.isnan(g[1:])
+        if q is not None:
+            valid &= np.asarray(q)[:-1] >= 0
+        E = 0.5 * (g[:-1] + g[1:]) * np.abs(p0[1:] - p0[:-1])[:, None] / r[None, :]
+        dd = d[1:] - d[:-1]
+        D = np.abs(dd)
+        A = np.sqrt(E * D) / (sigma * bref.SQRT_2PI)
+        Tm = 0.5 * (ts[:-1] + ts[1:])
+        pm = 0.5 * (pd[:-1] + pd[1:])
+        hk = np.where(D > 0, 0.5 * ((pd[1:] - pd[:-1]) / dd), 0.0) if curvature else np.zeros(D.shape)
+        for s in range(S):
+            if r[s] == 0:
+                re[:, s] = im[:, s] = asum[:, s] = Asum[:, s] = np.nan
+                continue
+            b2 = 2.0 * bottom[s]
+            for k in np.flatnonzero(valid[:, s]):
+                m, sg = mid[k, s], sigma[k, s]
+                qk = 0 if q is None else int(q[k][s])
+                for ctr, mirror, dq in ((m, None, 0), (-m, 0.0, 2), (b2 - m, b2, 0)):
+                    reach = sg * 4.001                   # candidates: a superset of the receivers within 4 sigma
+                    j0, j1 = np.searchsorted(ds, ctr - reach, side="left"), np.searchsorted(ds, ctr + reach, side="right")
+                    if not j1 > j0:
+                        continue
+                    j = order[j0:j1]
+                    u = (depths[j] - ctr) / sg
+                    v = u * u
+                    j, v = j[v <= 16], v[v <= 16]
+                    if len(j) == 0:
+                        continue
+                    dj = depths[j]
+                    e = dj - m if mirror is None else (mirror - dj) - m
+                    a = A[k, s] * bref.gexp(-0.5 * v)
+                    tau = Tm[k, s] + (pm[k, s] * e + hk[k, s] * (e * e))
+                    y = f * tau
+                    y = y - np.rint(y)
+                    t = y - 0.25 * ((qk + dq) & 3)
+                    t = t - np.rint(t)
+                    re[j, s] = re[j, s] + a * cref.gcos2pi(t)
+                    im[j, s] = im[j, s] + a * cref.gsin2pi(t)
+                    asum[j, s] = asum[j, s] + a
+                    Asum[j, s] = Asum[j, s] + A[k, s]
+    return (re, im, asum, Asum) if detail else (re, im)
+
+
+def fan_beam_pressure(rays, depths, environment, f, w_min=10.0, curvature=True, flatearth=True, W=None, nb=None, ns=None,
+                      q=None, cols=None):
+    """beam_pressure_field's definition on a host fan: the frame, the bathymetry and p0 as beam_reference.fan_beam_intensity
+    prepares them, q from the restated caustic index and the per-sample counts nb / ns (M, S) (None: a fan without bounces)
+    -> complex (R, S); with `cols` only those save columns (R, len(cols)) (the source's column is kept for r)."""
+    from pygenray_amd.host_physics import bilinear_interp
+    from pygenray_amd.launch_rays import _initial_slowness
+    xf, cin, rin, zin, bd, br = bref.frame_tables(np.asarray(rays.rs, dtype=float)[0], environment, flatearth)
+    c_source = bilinear_interp(xf[0], float(rays.source_depths[0]), rin, zin, cin)
+    p0 = _initial_slowness(rays.thetas, c_source)
+    zs, ps, ts = (np.asarray(a, dtype=float) for a in (rays.zs, rays.ps, rays.ts))
+    if q is None:
+        q = cref.tube_phase(cref.caustic_index(-zs, nb, ns), nb, ns)
+    bottom = bref.bottom_depths(xf, bd, br)
+    sel = slice(None) if cols is None else np.concatenate([[0], np.asarray(cols, dtype=np.int64)])
+    Wc = None if W is None else np.asarray(W)[:, sel]
+    re, im = beam_pressure(zs[:, sel], ps[:, sel], ts[:, sel], xf[sel], p0, depths, cin, rin, zin, bottom[sel], w_min, Wc,
+                           np.asarray(q)[:, sel], f, curvature)
+    p = cref.as_complex(re, im)
+    return p if cols is None else p[:, 1:]
+
+
+# ---- exact straight rays in an isovelocity half space: Lloyd's mirror and the free field ------------------------------------
+# c = 1500 m/s under a pressure-release surface, 4001 rays over +-40 degrees, 50 Hz.  A ray's unfolded depth at range r is
+# z_s + r tan(theta); folded at the surface its depth is the absolute value, its slowness changes sign and it has one surface
+# bounce (q = 2).  A tube whose two rays' counts differ is folded: q = -1.  The bottom is put out of every beam's reach.
+
+EXACT_C, EXACT_F, EXACT_N, EXACT_APERTURE = 1500.0, 50.0, 4001, 40.0
+EXACT_RANGES = np.array([2e3, 3e3, 4e3, 5e3])
+EXACT_BOTTOM = 1e6
+EXACT_RIN, EXACT_ZIN = np.array([0.0, 1e4]), np.array([0.0, 2e4])
+EXACT_CIN = np.full((2, 2), EXACT_C)
+LLOYD_ZS = 200.0
+LLOYD_DEPTHS = np.arange(75.0, 926.0, 50.0)
+FREE_ZS = 5000.0                                         # the steepest ray climbs 4195 m in 5 km: no ray reaches the surface
+FREE_DEPTHS = FREE_ZS + np.arange(-425.0, 426.0, 50.0)
+WIDTHS = (1.0, 3.0, 10.0)
+
+# The worst e = |p - p_ref| / sqrt(1 / R1^2 + 1 / R2^2) of the restatement over the four ranges, per min_width, with the
+# curvature term and without it (tests/test_beam_pressure_host.py prints them); every bound is twice its value.
+LLOYD_MEASURED = {1.0: 1.667551e-04, 3.0: 1.444394e-04, 10.0: 1.141209e-04}
+LLOYD_MEASURED_LINEAR = {1.0: 1.786286e-04, 3.0: 6.550833e-04, 10.0: 7.264197e-03}
+# The free field at min_width = 10 m with the curvature term: the worst | |p| R - 1 | and the worst phase difference from
+# 2 pi f R / c in radians
+FREE_MEASURED_AMPLITUDE = 8.235645e-05
+FREE_MEASURED_PHASE = 1.598978e-05
+
+
+# The rigid waveguide of wave_reference on the CPU oracle's fan (min_width 10 m, curvature on): the worst e over the 74 cells
+# section 16 keeps and over the 16 cells its edge rule drops.  The tube sum's worst on the 74 cells is wave_reference.GUIDE_MEASURED,
+# 1.3e-4: the beams' median there is lower (9.2e-5) and their worst 95 times higher, at receivers within reach of the two
+# beams beside a folded tube, which section 10 makes as wide as that tube (up to tan(40 deg) dx = 84 m); DESIGN.md section 20.
+GUIDE_BEAM_MEASURED = 1.234803e-02
+GUIDE_BEAM_DROPPED_MEASURED = 1.610692e-01
+
+
+def exact_fan(source_depth, ranges=EXACT_RANGES):
+    """-> (zs, ps, ts (M, 1 + len(ranges)) stored convention, x, p0, q (M, S)): the straight rays of a source at
+    `source_depth` at the ranges (column 0 is the source's own), folded at the surface"""
+    th = np.radians(np.linspace(-EXACT_APERTURE, EXACT_APERTURE, EXACT_N))
+    p0 = np.sin(th) / EXACT_C
+    x = np.concatenate([[0.0], np.asarray(ranges, dtype=float)])
+    zu = source_depth + x[None, :] * np.tan(th)[:, None]             # + down
+    refl = zu < 0
+    depth = np.abs(zu)
+    p = np.where(refl, -p0[:, None], p0[:, None])
+    T = x[None, :] / (EXACT_C * np.cos(th))[:, None]
+    ns = refl.astype(np.int64)
+    q = np.zeros(zu.shape, np.int32)
+    q[:-1] = np.where(ns[:-1] == ns[1:], 2 * ns[:-1], -1)
+    return -depth, -p, T, x, p0, q
+
+
+def exact_pressure(source_depth, depths, w_min, curvature, ranges=EXACT_RANGES):
+    """the restatement on exact_fan -> complex (len(depths), len(ranges))"""
+    zs, ps, ts, x, p0, q = exact_fan(source_depth, ranges)
+    re, im = beam_pressure(zs, ps, ts, x, p0, depths, EXACT_CIN, EXACT_RIN, EXACT_ZIN, np.full(len(x), EXACT_BOTTOM), w_min,
+                           None, q, EXACT_F, curvature)
+    return cref.as_complex(re, im)[:, 1:]
+
+
+def lloyd_error(p, source_depth=LLOYD_ZS, depths=LLOYD_DEPTHS, ranges=EXACT_RANGES):
+    """e of p (len(depths), len(ranges)) against exp(i k R1) / R1 - exp(i k R2) / R2, in units of the incoherent amplitude"""
+    D, X = np.asarray(depths, dtype=float)[:, None], np.asarray(ranges, dtype=float)[None, :]
+    R1, R2 = np.hypot(X, D - source_depth), np.hypot(X, D + source_depth)
+    k = 2.0 * np.pi * EXACT_F / EXACT_C
+    ref = np.exp(1j * k * R1) / R1 - np.exp(1j * k * R2) / R2
+    return np.abs(p - ref) / np.sqrt(1.0 / R1 ** 2 + 1.0 / R2 ** 2)
+
+
+def widest_beam(source_depth, w_min, ranges=EXACT_RANGES):
+    """the largest sigma of exact_fan's tubes per range (len(ranges),)"""
+    zs, ps, ts, x, p0, q = exact_fan(source_depth, ranges)
+    sigma = bref._tubes(zs, ps, x, p0, EXACT_CIN, EXACT_RIN, EXACT_ZIN, w_min)[2]
+    return sigma[:, 1:].max(axis=0)
