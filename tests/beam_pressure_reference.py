@@ -14,7 +14,9 @@ def beam_pressure(zs, ps, ts, x, p0, depths, cin, rin, zin, bottom, w_min, W, q,
     x (S,) save ranges in the frame of the tables, p0 (M,), bottom (S,), weights W (M, S) or None, phase index q (M, S)
     integers or None, frequency f -> (re, im), each (len(depths), S).  Per column the tubes in increasing k, per tube the
     centres m, -m, 2 b - m, every kept term added to its receiver's two sums one at a time.  With `detail` also, per receiver,
-    the sum of a in the same order and the sum of A' over the kept terms."""
+    the sum of a in the same order and the sum of A' over the kept terms, and a dict of counters per tube and column: `kept`
+    (3, M - 1, S) the receivers at which the terms of the centres m, -m, 2 b - m were kept, `live` (M - 1, S) the tubes that
+    add their terms, `valid` the same whatever q says, and `sigma` (M - 1, S)."""
     zs, ps, ts, x, depths, bottom = (np.asarray(a, dtype=float) for a in (zs, ps, ts, x, depths, bottom))
     d, pd = -zs, -ps
     M, S = d.shape
@@ -24,10 +26,12 @@ def beam_pressure(zs, ps, ts, x, p0, depths, cin, rin, zin, bottom, w_min, W, q,
     order = np.argsort(depths, kind="stable")
     ds = depths[order]
     re, im, asum, Asum = (np.zeros((R, S)) for _ in range(4))
+    kept = np.zeros((3, max(M - 1, 0), S), np.int64)
     with np.errstate(invalid="ignore", divide="ignore", over="ignore"):
         valid = ~np.isnan(g[:-1]) & ~np.isnan(g[1:])
+        whatever_q = valid & (r != 0)[None, :]
         if q is not None:
-            valid &= np.asarray(q)[:-1] >= 0
+            valid = valid & (np.asarray(q)[:-1] >= 0)
         E = 0.5 * (g[:-1] + g[1:]) * np.abs(p0[1:] - p0[:-1])[:, None] / r[None, :]
         dd = d[1:] - d[:-1]
         D = np.abs(dd)
@@ -43,7 +47,7 @@ def beam_pressure(zs, ps, ts, x, p0, depths, cin, rin, zin, bottom, w_min, W, q,
             for k in np.flatnonzero(valid[:, s]):
                 m, sg = mid[k, s], sigma[k, s]
                 qk = 0 if q is None else int(q[k][s])
-                for ctr, mirror, dq in ((m, None, 0), (-m, 0.0, 2), (b2 - m, b2, 0)):
+                for ci, (ctr, mirror, dq) in enumerate(((m, None, 0), (-m, 0.0, 2), (b2 - m, b2, 0))):
                     reach = sg * 4.001                   # candidates: a superset of the receivers within 4 sigma
                     j0, j1 = np.searchsorted(ds, ctr - reach, side="left"), np.searchsorted(ds, ctr + reach, side="right")
                     if not j1 > j0:
@@ -54,6 +58,7 @@ def beam_pressure(zs, ps, ts, x, p0, depths, cin, rin, zin, bottom, w_min, W, q,
                     j, v = j[v <= 16], v[v <= 16]
                     if len(j) == 0:
                         continue
+                    kept[ci, k, s] = len(j)
                     dj = depths[j]
                     e = dj - m if mirror is None else (mirror - dj) - m
                     a = A[k, s] * bref.gexp(-0.5 * v)
@@ -66,7 +71,32 @@ def beam_pressure(zs, ps, ts, x, p0, depths, cin, rin, zin, bottom, w_min, W, q,
                     im[j, s] = im[j, s] + a * cref.gsin2pi(t)
                     asum[j, s] = asum[j, s] + a
                     Asum[j, s] = Asum[j, s] + A[k, s]
-    return (re, im, asum, Asum) if detail else (re, im)
+    if detail:
+        return re, im, asum, Asum, dict(kept=kept, live=valid & (r != 0)[None, :], valid=whatever_q, sigma=sigma)
+    return re, im
+
+
+def eikonal_share(zs, ps, ts, nb, ns, x, detail=False):
+    """The sign of the slowness, held by the eikonal equation alone: at a fixed range T_k+1 - T_k ~ p_m (d_k+1 - d_k) for
+    p = dT/dd, so the two sides have one sign wherever the fan is smooth.  zs / ps / ts (M, S) stored convention (d = -zs,
+    pd = -ps), nb / ns (M, S) the bounce counts per sample (None: no ray bounces), x (S,) the save ranges -> the share of the
+    eligible tubes at which the signs agree (NaN: none eligible); with `detail` also their number.  Eligible: a column other
+    than the source's, T, d and p of both rays finite, nb and ns equal at both rays, |p_m (d_k+1 - d_k)| > 1e-9 s.  A fan
+    read in the other convention of p gives one minus the share."""
+    zs, ps, ts, x = (np.asarray(a, dtype=float) for a in (zs, ps, ts, x))
+    d, pd = -zs, -ps
+    with np.errstate(invalid="ignore", over="ignore"):
+        dT = ts[1:] - ts[:-1]
+        rhs = (0.5 * (pd[:-1] + pd[1:])) * (d[1:] - d[:-1])
+        ok = np.isfinite(ts) & np.isfinite(d) & np.isfinite(pd)
+        ok = ok[:-1] & ok[1:] & (x != x[0])[None, :]
+        for n in (nb, ns):
+            if n is not None:
+                ok &= np.asarray(n)[:-1] == np.asarray(n)[1:]
+        ok &= np.abs(rhs) > 1e-9
+    n = int(ok.sum())
+    share = float(((dT[ok] > 0) == (rhs[ok] > 0)).mean()) if n else float("nan")
+    return (share, n) if detail else share
 
 
 def fan_beam_pressure(rays, depths, environment, f, w_min=10.0, curvature=True, flatearth=True, W=None, nb=None, ns=None,

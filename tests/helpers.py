@@ -235,3 +235,10 @@ def random_case(seed, n_rays=128):
     desc = (f"nz {len(z):5d} ({['uniform', 'pow2', 'stretched'][kind_z]}) nr {len(r):3d} nb {nb:2d} rtol {rtol:g} S {S:2d} "
             f"range-dep {bool(slope)!s:5s} mirrored {mirrored!s:5s} x0 {x0:10.0f} x1 {x1:10.0f}")
     return arrs, (src, x0, th), dict(x0=x0, x1=x1, S=S, rtol=rtol, terminate_backwards=tb), desc
+
+
+def sign_flipped(a, b):
+    """True when float64 `a` holds the bits of `b` with the sign bit flipped, entry for entry, NaNs and zeros included: what a
+    fan in the ODE sign holds of z and p against the same fan in the stored sign"""
+    a, b = np.ascontiguousarray(a, dtype=np.float64), np.ascontiguousarray(b, dtype=np.float64)
+    return a.shape == b.shape and bool(np.array_equal(a.view(np.uint64) ^ np.uint64(1 << 63), b.view(np.uint64)))

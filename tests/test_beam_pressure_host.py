@@ -124,8 +124,8 @@ def test_a_caustic_stays_bounded(curvature):
     assert d[10] < depths[0] < d[11] and max(depths[0] - d[10], d[11] - depths[0]) <= 1e-6 and (np.diff(d) > 0).all()
     tab = (bp.EXACT_CIN, bp.EXACT_RIN, bp.EXACT_ZIN)
     tre, tim = cref.tube_pressure(zs, ps, ts, x, p0, depths, *tab, None, None, 50.0)
-    re, im, asum, Asum = bp.beam_pressure(zs, ps, ts, x, p0, depths, *tab, np.full(2, bp.EXACT_BOTTOM), 10.0, None, None, 50.0,
-                                          curvature, detail=True)
+    re, im, asum, Asum, _ = bp.beam_pressure(zs, ps, ts, x, p0, depths, *tab, np.full(2, bp.EXACT_BOTTOM), 10.0, None, None, 50.0,
+                                             curvature, detail=True)
     tube, beam = np.hypot(tre[0, 1], tim[0, 1]), np.hypot(re[0, 1], im[0, 1])
     print(f"a tube 1e-6 m wide at the receiver, curvature {curvature}: tube sum |p| {tube:.4e}, beam sum |p| {beam:.4e}, "
           f"sum of A' {Asum[0, 1]:.4e}")
@@ -170,7 +170,7 @@ def test_identities(folded):
     zs, ps, ts, x, p0, qf = bp.exact_fan(bp.FREE_ZS)
     free = dict(zs=zs, ps=ps, ts=ts, x=x, p0=p0, depths=bp.FREE_DEPTHS, cin=bp.EXACT_CIN, rin=bp.EXACT_RIN, zin=bp.EXACT_ZIN,
                 bottom=np.full(len(x), bp.EXACT_BOTTOM), w_min=10.0, W=None)
-    r0, i0, asum, _ = bp.beam_pressure(**free, q=qf, f=0.0, detail=True)
+    r0, i0, asum, _, _ = bp.beam_pressure(**free, q=qf, f=0.0, detail=True)
     assert (qf == 0).all() and _same(r0, asum) and (asum[:, 1:] > 0).all()
     assert (i0[:, 1:] == 0).all() and not np.signbit(i0[:, 1:]).any()
     rn, in_ = bp.beam_pressure(**free, q=None, f=0.0)
@@ -194,6 +194,39 @@ def test_identities(folded):
     # sum to which nothing was added stays +0.0)
     r2, i2 = bp.beam_pressure(**args, q=np.where(q >= 0, q + 2, q), f=50.0)
     assert _same(r2, -re) and _same(i2, -im) and (re[:, 1:] != 0).mean() > 0.9
+
+
+# ---- the helpers of the random-environment sweep can fail ---------------------------------------------------------------------
+
+@pytest.mark.parametrize("source_depth", [bp.FREE_ZS, bp.LLOYD_ZS])
+def test_the_eikonal_share_tells_the_sign_of_p(source_depth):
+    """straight rays with the exact p = dT/dd: every eligible tube agrees, and not one with p in the other sign"""
+    zs, ps, ts, x, p0, q = bp.exact_fan(source_depth)
+    th = np.radians(np.linspace(-bp.EXACT_APERTURE, bp.EXACT_APERTURE, bp.EXACT_N))
+    ns = (source_depth + x[None, :] * np.tan(th)[:, None] < 0).astype(np.int64)        # exact_fan's own fold
+    assert ns.any() == (source_depth == bp.LLOYD_ZS) and np.array_equal(q[:-1] == -1, ns[:-1] != ns[1:])
+    nb = np.zeros_like(ns)
+    share, tubes = bp.eikonal_share(zs, ps, ts, nb, ns, x, detail=True)
+    assert share == 1.0 and tubes >= 0.99 * (bp.EXACT_N - 1) * len(bp.EXACT_RANGES)
+    assert bp.eikonal_share(zs, -ps, ts, nb, ns, x, detail=True) == (0.0, tubes)
+    assert bp.eikonal_share(zs, ps, ts, None, None, x) == (1.0 if not ns.any() else pytest.approx(1.0, abs=1e-3))
+    # a tube across a fold is not eligible, nor is the source's column, nor a tube with a NaN
+    assert bp.eikonal_share(zs, ps, ts, nb, ns + 2 * np.arange(len(ns))[:, None], x, detail=True)[1] == 0
+    assert np.isnan(bp.eikonal_share(zs[:, :1], ps[:, :1], ts[:, :1], None, None, x[:1]))
+    holed = ts.copy()
+    holed[7, 2] = np.nan
+    assert bp.eikonal_share(zs, ps, holed, nb, ns, x, detail=True) == (1.0, tubes - 2)
+
+
+def test_the_sign_bit_comparison_can_fail():
+    from helpers import sign_flipped
+    a = np.array([1.5, -2.0, 0.0, -0.0, np.nan, -np.nan, np.inf, 5e-324])
+    assert sign_flipped(-a, a) and sign_flipped(a, -a) and not sign_flipped(a, a)
+    for i in range(len(a)):
+        b = -a
+        b[i] = a[i]                                                                 # one entry's sign left as it was
+        assert not sign_flipped(b, a), i
+    assert not sign_flipped(-a[:-1], a) and not sign_flipped(np.abs(a), a)
 
 
 # ---- exports, prototypes, refusals --------------------------------------------------------------------------------------------
