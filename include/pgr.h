@@ -584,6 +584,11 @@ int pgr_boundary_loss_device(pgr_env* env, const double* bx, const double* bp, c
  * pgr_beam_pressure_device_w.  Part of this ABI, stated in a file of its own beside this one. ---- */
 #include "pgr_beam_coherent.h"
 
+/* ---- Gaussian-beam arrivals, the terms of the coherent beam sum listed per receiver:
+ * pgr_fan_beam_arrival_counts_w, pgr_fan_beam_arrivals_w, pgr_beam_arrival_counts_device_w, pgr_beam_arrivals_device_w.  Part
+ * of this ABI, stated in a file of its own beside this one. ---- */
+#include "pgr_beam_arrivals.h"
+
 /* What this build of the library is: whether the instruction-layout pass of the build was applied
  * ("relaid: 502 -> 31 straddles ..." or "plain hipcc") and which arithmetic variant was compiled.
  * bench.py puts it into its JSON line so that a measured number names the binary it came from. */

@@ -130,6 +130,13 @@ try:
         BEAM_COHERENT_PROTOTYPES = parse_header(_f.read())[0]
 except OSError as _e:
     raise PgrError(f"{BEAM_COHERENT_HEADER}: the C ABI header cannot be read ({_e})") from None
+# ... and the terms of that beam sum listed as arrivals, likewise
+BEAM_ARRIVALS_HEADER = os.path.join(_HERE, "..", "include", "pgr_beam_arrivals.h")
+try:
+    with open(BEAM_ARRIVALS_HEADER) as _f:
+        BEAM_ARRIVALS_PROTOTYPES = parse_header(_f.read())[0]
+except OSError as _e:
+    raise PgrError(f"{BEAM_ARRIVALS_HEADER}: the C ABI header cannot be read ({_e})") from None
 globals().update(_CONSTANTS)   # PGR_TERMINATE_BACKWARDS, PGR_SAMPLE_MAJOR, ... PGR_OPT_D2H_REGISTER
 
 _REBUILD = "`python -c 'import __graft_entry__ as g; g.build()'`"
@@ -216,7 +223,8 @@ def build(force=False, verbose=False, out=None, extra_flags=()):
     src = os.path.join(CSRC, "pgr_hip.hip")
     hdr = os.path.join(_HERE, "..", "include", "pgr.h")
     # (one translation unit: pgr_hip.hip includes every csrc/*.h -- device building blocks, the fan kernel, the host side in pieces)
-    deps = [src, hdr, COHERENT_HEADER, SIGNAL_HEADER, SPECTRUM_HEADER, REFLECTION_HEADER, BEAM_COHERENT_HEADER, os.path.join(_HERE, "_isa_layout.py")] + sorted(
+    deps = [src, hdr, COHERENT_HEADER, SIGNAL_HEADER, SPECTRUM_HEADER, REFLECTION_HEADER, BEAM_COHERENT_HEADER, BEAM_ARRIVALS_HEADER,
+            os.path.join(_HERE, "_isa_layout.py")] + sorted(
         os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h"))
     if not force and os.path.exists(LIB_PATH):
         if os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(d) for d in deps):
@@ -281,11 +289,11 @@ def load():
             "). pygenray_amd has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
     for name, (restype, argtypes) in {**PROTOTYPES, **COHERENT_PROTOTYPES, **SIGNAL_PROTOTYPES, **SPECTRUM_PROTOTYPES,
-                                      **REFLECTION_PROTOTYPES, **BEAM_COHERENT_PROTOTYPES}.items():
+                                      **REFLECTION_PROTOTYPES, **BEAM_COHERENT_PROTOTYPES, **BEAM_ARRIVALS_PROTOTYPES}.items():
         try:
             fn = getattr(L, name)
         except AttributeError:
-            raise PgrError(f"{LIB_PATH} does not export {name}, which include/pgr.h declares (itself or through pgr_coherent.h / pgr_signal.h / pgr_spectrum.h / pgr_reflection.h / pgr_beam_coherent.h): the library is older than "
+            raise PgrError(f"{LIB_PATH} does not export {name}, which include/pgr.h declares (itself or through pgr_coherent.h / pgr_signal.h / pgr_spectrum.h / pgr_reflection.h / pgr_beam_coherent.h / pgr_beam_arrivals.h): the library is older than "
                            f"the header. Rebuild it: {_REBUILD}.") from None
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -652,6 +660,25 @@ class FanHandle:
                                              depths_ptr, int(n_depths), float(min_width), int(bool(curvature)), re_ptr, im_ptr,
                                              stream))
 
+    def beam_arrival_counts(self, p0_ptr, q_ptr, bottom_ptr, depths_ptr, n_depths, min_width, cols, counts_ptr, stream=0,
+                            weights=0):
+        """pgr_fan_beam_arrival_counts_w on raw device pointers (ints): counts[n_depths][len(cols)] (int64) = the terms
+        ``beam_pressure`` adds at each receiver depth and requested column; `cols` a host sequence of column indices, the
+        other arguments ``beam_pressure``'s (include/pgr_beam_arrivals.h)."""
+        c = np.ascontiguousarray(cols, dtype=np.int32)
+        check(load().pgr_fan_beam_arrival_counts_w(self._h, p0_ptr, weights or None, q_ptr or None, bottom_ptr, depths_ptr,
+                                                   int(n_depths), float(min_width), _addr(c), len(c), counts_ptr, stream))
+
+    def beam_arrivals(self, p0_ptr, q_ptr, bottom_ptr, depths_ptr, n_depths, min_width, cols, curvature, offsets_ptr, n_arrivals,
+                      tube_ptr, image_ptr, time_ptr, amp_ptr, qa_ptr, stream=0, weights=0):
+        """pgr_fan_beam_arrivals_w: those terms themselves, written from offsets[j * len(cols) + c] into tube, image, qa
+        (int32) and time, amplitude (float64), device pointers holding n_arrivals each."""
+        c = np.ascontiguousarray(cols, dtype=np.int32)
+        check(load().pgr_fan_beam_arrivals_w(self._h, p0_ptr, weights or None, q_ptr or None, bottom_ptr, depths_ptr,
+                                             int(n_depths), float(min_width), _addr(c), len(c), int(bool(curvature)),
+                                             offsets_ptr, int(n_arrivals), tube_ptr, image_ptr, time_ptr, amp_ptr, qa_ptr,
+                                             stream))
+
     def close(self):
         if getattr(self, "_h", None):
             load().pgr_fan_destroy(self._h)
@@ -860,6 +887,29 @@ def beam_pressure_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_
     check(load().pgr_beam_pressure_device_w(env._h, t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr,
                                             weights or None, q_ptr or None, float(frequency), bottom_ptr, depths_ptr,
                                             int(n_depths), float(min_width), int(bool(curvature)), re_ptr, im_ptr, stream))
+
+
+def beam_arrival_counts_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, q_ptr, bottom_ptr, depths_ptr,
+                               n_depths, min_width, cols, counts_ptr, stream=0, weights=0):
+    """pgr_beam_arrival_counts_device_w on raw device pointers (ints; q / weights 0: absent): the terms ``beam_pressure_device``
+    adds per receiver depth and requested column of `cols` (a host sequence), of caller buffers T / z / p [n_samples][n_rays]
+    (stored sign convention) on `env` (an EnvHandle); see include/pgr_beam_arrivals.h."""
+    c = np.ascontiguousarray(cols, dtype=np.int32)
+    check(load().pgr_beam_arrival_counts_device_w(env._h, t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr,
+                                                  weights or None, q_ptr or None, bottom_ptr, depths_ptr, int(n_depths),
+                                                  float(min_width), _addr(c), len(c), counts_ptr, stream))
+
+
+def beam_arrivals_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, q_ptr, bottom_ptr, depths_ptr, n_depths,
+                         min_width, cols, curvature, offsets_ptr, n_arrivals, tube_ptr, image_ptr, time_ptr, amp_ptr, qa_ptr,
+                         stream=0, weights=0):
+    """pgr_beam_arrivals_device_w on raw device pointers (ints): beam_arrival_counts_device's walk, writing the arrivals; see
+    include/pgr_beam_arrivals.h."""
+    c = np.ascontiguousarray(cols, dtype=np.int32)
+    check(load().pgr_beam_arrivals_device_w(env._h, t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr,
+                                            weights or None, q_ptr or None, bottom_ptr, depths_ptr, int(n_depths),
+                                            float(min_width), _addr(c), len(c), int(bool(curvature)), offsets_ptr,
+                                            int(n_arrivals), tube_ptr, image_ptr, time_ptr, amp_ptr, qa_ptr, stream))
 
 
 def signal_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, tstart_ptr, frequency, inv_sigma, dt, n_times, re_ptr,

@@ -67,7 +67,8 @@ __device__ __forceinline__ void gbc_chunk_tubes(const GbArgs& g, const Ctx<false
 }
 
 // one term: the beam centred at ctr, seen from depth d (gb_term's tests), the receiver at e in the beam's own space and qk
-// quarter cycles
+// quarter cycles.  (Its two tests, a and tau have a twin, gbc_kept in pgr_beam_arrivals.h, which lists these terms as arrivals:
+// an edit here is mirrored there, statement for statement.)
 __device__ __forceinline__ void gbc_term(double& re, double& im, double f, double d, double ctr, double e, double sig, double A,
                                          double Tm, double pm, double hk, int qk)
 {
@@ -90,7 +91,9 @@ __device__ __forceinline__ void gbc_term(double& re, double& im, double f, doubl
     }
 }
 
-// pass 2: one wave per (column, band of 64 receivers)
+// pass 2: one wave per (column, band of 64 receivers).  (The walk below -- the chunk test, the tubes in order, the centres the
+// mask keeps -- has a twin, gbc_walk in pgr_beam_arrivals.h: an edit here is mirrored there; sharing it changed this kernel's
+// machine code)
 __global__ void __launch_bounds__(64) pgr_gbc_sum(EnvDev env, GbArgs g, CohOut o, int curv)
 {
     __shared__ GbcTubes L;

@@ -72,9 +72,11 @@ __device__ __forceinline__ void gb_shape(double wmin, double d, double& mid, dou
 
 // pass 1: the depths chunk c's beams reach in column s, [lo, hi] (tubes with a NaN centre ignored; none: [+inf, -inf]).
 // Widened by 2^-40 of its magnitude, which covers the rounding of m -+ sigma GB_REACH and of the receiver's d - m.
-__global__ void __launch_bounds__(256) pgr_gb_bounds(GbArgs g)
+// (column slot blockIdx.y is column s: the slot itself, or with COLS the caller's cols[slot], pgr_beam_arrivals.h)
+template <bool COLS>
+__device__ __forceinline__ void gb_bounds(const GbArgs& g)
 {
-    const int s = blockIdx.y;
+    const int s = COLS ? tl_column(g, blockIdx.y) : (int)blockIdx.y;
     tube_bounds<GB_TUBES, -1, true>(g, [&](int t, int64_t m, double& lo, double& hi) {
         double d = NAN;                              // (rays outside 0 .. M-1 are NaN)
         if (m >= 0 && m < g.M) d = g.zsign * g.Z[tl_index(g, s, m)];
@@ -87,6 +89,8 @@ __global__ void __launch_bounds__(256) pgr_gb_bounds(GbArgs g)
         }
     });
 }
+
+__global__ void __launch_bounds__(256) pgr_gb_bounds(GbArgs g) { gb_bounds<false>(g); }
 
 // the LDS of one wave's walk: the current chunk's tubes (m NaN where the tube adds nothing)
 struct GbTubes { double m[64], sig[64], A[64]; };

@@ -61,6 +61,7 @@
 #include "pgr_bounce.h"         // boundary reflection loss from a fan's bounce log: pgr_fan_boundary_loss, pgr_boundary_loss_device
 #include "pgr_phase.h"          // caustic index of the tubes and their coherent sum: pgr_fan_caustic_index, pgr_fan_pressure_w, ..._device
 #include "pgr_beam_phase.h"     // coherent Gaussian-beam pressure with wavefront curvature: pgr_fan_beam_pressure_w, pgr_beam_pressure_device_w
+#include "pgr_beam_arrivals.h"  // the terms of that sum listed as arrivals: pgr_fan_beam_arrival_counts_w, pgr_fan_beam_arrivals_w, ..._device_w
 #include "pgr_signal.h"         // received time series of a Gaussian pulse from the arrivals: pgr_signal_device
 #include "pgr_reflect.h"        // the coherent sums with a lag per arrival (complex bottom reflection): pgr_fan_pressure_phi, pgr_signal_device_phi, ...
 #include "pgr_spectrum.h"       // transfer function of the arrivals over a frequency band: pgr_spectrum_device

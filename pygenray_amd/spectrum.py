@@ -128,6 +128,34 @@ def _fft_sizes(n_source, n_times, n_fft):
     return nt, nf
 
 
+def _synthesise(H_of, source, dt, carrier, t0, n_times, n_fft):
+    """``received_waveform``'s checks and its FFT synthesis around a transfer function: ``H_of(frequencies, t_reduce)`` -> H
+    (R, n, n_fft), as ``transfer_function`` gives it -> u (R, n, n_times).  Shared with ``beam_received_waveform``."""
+    s = np.asarray(source)
+    if s.ndim != 1 or len(s) == 0:
+        raise ValueError("source must be a non-empty 1-D sequence of complex baseband samples")
+    s = s.astype(np.complex128)
+    if not np.all(np.isfinite(s)):
+        raise ValueError("source must be finite")
+    step, fc = float(dt), float(carrier)
+    if not (np.isfinite(step) and step > 0):
+        raise ValueError("dt must be finite and > 0 seconds")
+    if not (np.isfinite(fc) and fc >= 1.0 / (2.0 * step)):
+        raise ValueError("carrier must be finite and at least 1 / (2 dt) Hz: the band carrier +- 1 / (2 dt) must not reach "
+                         "negative frequencies")
+    nt, nf = _fft_sizes(len(s), n_times, n_fft)
+    start = np.asarray(t0, dtype=float)
+    if not np.all(np.isfinite(start)):
+        raise ValueError("t0 must be finite")
+    nu = np.fft.fftfreq(nf, step)
+    Shat = nf * np.fft.ifft(s, nf)
+    H = H_of(fc + nu, start)
+    cyc = fc * np.broadcast_to(start, (H.shape[1],))
+    turn = np.exp(2j * np.pi * (cyc - np.rint(cyc)))
+    u = np.fft.fft(Shat * H, axis=-1) / nf * turn[None, :, None]
+    return np.ascontiguousarray(u[:, :, :nt])
+
+
 def received_waveform(rays, receiver_depths, env, source, dt, carrier, t0, n_times=None, n_fft=None, range_indices=None,
                       absorption=None, bottom_loss=None, surface_loss=None, flatearth=True, device=0):
     """The signal a receiver records when the source sends ANY waveform: the complex baseband envelope ``source[i]`` (a
@@ -151,31 +179,11 @@ def received_waveform(rays, receiver_depths, env, source, dt, carrier, t0, n_tim
     frequency across the band.  ``ValueError`` for a ``carrier`` below 1 / (2 dt) (the band would reach negative
     frequencies), ``n_fft < len(source)`` and ``n_times > n_fft``; every other argument, error and the device residency are
     ``transfer_function``'s."""
-    s = np.asarray(source)
-    if s.ndim != 1 or len(s) == 0:
-        raise ValueError("source must be a non-empty 1-D sequence of complex baseband samples")
-    s = s.astype(np.complex128)
-    if not np.all(np.isfinite(s)):
-        raise ValueError("source must be finite")
-    step, fc = float(dt), float(carrier)
-    if not (np.isfinite(step) and step > 0):
-        raise ValueError("dt must be finite and > 0 seconds")
-    if not (np.isfinite(fc) and fc >= 1.0 / (2.0 * step)):
-        raise ValueError("carrier must be finite and at least 1 / (2 dt) Hz: the band carrier +- 1 / (2 dt) must not reach "
-                         "negative frequencies")
-    nt, nf = _fft_sizes(len(s), n_times, n_fft)
-    start = np.asarray(t0, dtype=float)
-    if not np.all(np.isfinite(start)):
-        raise ValueError("t0 must be finite")
-    nu = np.fft.fftfreq(nf, step)
-    Shat = nf * np.fft.ifft(s, nf)
-    H = transfer_function(rays, receiver_depths, env, fc + nu, range_indices=range_indices, absorption=absorption,
-                          bottom_loss=bottom_loss, surface_loss=surface_loss, t_reduce=start, flatearth=flatearth,
-                          device=device)
-    cyc = fc * np.broadcast_to(start, (H.shape[1],))
-    turn = np.exp(2j * np.pi * (cyc - np.rint(cyc)))
-    u = np.fft.fft(Shat * H, axis=-1) / nf * turn[None, :, None]
-    return np.ascontiguousarray(u[:, :, :nt])
+    return _synthesise(lambda freq, start: transfer_function(rays, receiver_depths, env, freq, range_indices=range_indices,
+                                                             absorption=absorption, bottom_loss=bottom_loss,
+                                                             surface_loss=surface_loss, t_reduce=start, flatearth=flatearth,
+                                                             device=device),
+                       source, dt, carrier, t0, n_times, n_fft)
 
 
 __all__ = ["transfer_function", "received_waveform"]

@@ -245,13 +245,13 @@ class _FanFrame(_TracedFan):
     def run(self, entry, *args):
         """Tube entry `entry` on the fan, with p0, the arguments after it and the stream: ``FanHandle.<entry>`` on a
         device-resident fan, else ``_lib.<entry>_device`` on the host fan's trajectories (ts only for ``arrivals`` and
-        ``pressure`` / ``pressure_phi`` / ``beam_pressure``)."""
+        ``pressure`` / ``pressure_phi`` / ``beam_pressure`` / ``beam_arrival_counts`` / ``beam_arrivals``)."""
         args = (self.d_p0.data_ptr(),) + args + (self.stream,)
         # (the arrival counts have no weighted twin: finite weights leave the tubes counted as they are)
         kw = {"weights": self.d_W.data_ptr()} if self.d_W is not None and entry != "arrival_counts" else {}
         if self.handle is not None:
             return getattr(self.handle, entry)(*args, **kw)
-        fan = [self._host_fan(k) for k in (("ts", "zs", "ps") if entry in ("arrivals", "pressure", "pressure_phi", "beam_pressure") else ("zs", "ps"))]
+        fan = [self._host_fan(k) for k in (("ts", "zs", "ps") if entry in ("arrivals", "pressure", "pressure_phi", "beam_pressure", "beam_arrival_counts", "beam_arrivals") else ("zs", "ps"))]
         getattr(_lib, entry + "_device")(self.env, *fan, len(self.rays), len(self.x), self._host_fan("xf"), *args, **kw)
 
     def image(self):
