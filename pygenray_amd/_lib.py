@@ -89,54 +89,35 @@ def parse_header(text):
     return prototypes, constants
 
 
-try:
-    with open(HEADER) as _f:
-        PROTOTYPES, _CONSTANTS = parse_header(_f.read())
-except OSError as _e:
-    raise PgrError(f"{HEADER}: the C ABI header cannot be read ({_e}); pygenray_amd binds libpgr_hip.so from it and runs "
-                   "from its source tree") from None
-# ... and the part of it pgr.h includes from a file of its own: the caustic index and the coherent tube sum
-COHERENT_HEADER = os.path.join(_HERE, "..", "include", "pgr_coherent.h")
-try:
-    with open(COHERENT_HEADER) as _f:
-        COHERENT_PROTOTYPES = parse_header(_f.read())[0]
-except OSError as _e:
-    raise PgrError(f"{COHERENT_HEADER}: the C ABI header cannot be read ({_e})") from None
-# ... and the received signal of a Gaussian pulse, likewise
-SIGNAL_HEADER = os.path.join(_HERE, "..", "include", "pgr_signal.h")
-try:
-    with open(SIGNAL_HEADER) as _f:
-        SIGNAL_PROTOTYPES = parse_header(_f.read())[0]
-except OSError as _e:
-    raise PgrError(f"{SIGNAL_HEADER}: the C ABI header cannot be read ({_e})") from None
-# ... and the transfer function of the arrivals over a frequency band, likewise
-SPECTRUM_HEADER = os.path.join(_HERE, "..", "include", "pgr_spectrum.h")
-try:
-    with open(SPECTRUM_HEADER) as _f:
-        SPECTRUM_PROTOTYPES = parse_header(_f.read())[0]
-except OSError as _e:
-    raise PgrError(f"{SPECTRUM_HEADER}: the C ABI header cannot be read ({_e})") from None
-# ... and the coherent sums with a lag per arrival, the bottom's complex reflection coefficient, likewise
-REFLECTION_HEADER = os.path.join(_HERE, "..", "include", "pgr_reflection.h")
-try:
-    with open(REFLECTION_HEADER) as _f:
-        REFLECTION_PROTOTYPES = parse_header(_f.read())[0]
-except OSError as _e:
-    raise PgrError(f"{REFLECTION_HEADER}: the C ABI header cannot be read ({_e})") from None
-# ... and the coherent Gaussian-beam pressure with wavefront curvature, likewise
-BEAM_COHERENT_HEADER = os.path.join(_HERE, "..", "include", "pgr_beam_coherent.h")
-try:
-    with open(BEAM_COHERENT_HEADER) as _f:
-        BEAM_COHERENT_PROTOTYPES = parse_header(_f.read())[0]
-except OSError as _e:
-    raise PgrError(f"{BEAM_COHERENT_HEADER}: the C ABI header cannot be read ({_e})") from None
-# ... and the terms of that beam sum listed as arrivals, likewise
-BEAM_ARRIVALS_HEADER = os.path.join(_HERE, "..", "include", "pgr_beam_arrivals.h")
-try:
-    with open(BEAM_ARRIVALS_HEADER) as _f:
-        BEAM_ARRIVALS_PROTOTYPES = parse_header(_f.read())[0]
-except OSError as _e:
-    raise PgrError(f"{BEAM_ARRIVALS_HEADER}: the C ABI header cannot be read ({_e})") from None
+def _header_text(path):
+    try:
+        with open(path) as f:
+            return f.read()
+    except OSError as e:
+        raise PgrError(f"{path}: the C ABI header cannot be read ({e}); pygenray_amd binds libpgr_hip.so from it and runs "
+                       "from its source tree") from None
+
+
+def read_abi(header):
+    """The C ABI `header` (include/pgr.h) states, itself and in every `#include "pgr_*.h"` of it, in order -> (paths,
+    {file name: that header's own prototypes}, constants); a name two headers declare is an error."""
+    bare = re.sub(r"/\*.*?\*/|//[^\n]*", " ", _header_text(header), flags=re.S)
+    paths = [header] + [os.path.join(os.path.dirname(header), n)
+                        for n in re.findall(r'^[ \t]*#[ \t]*include[ \t]+"(pgr_\w+\.h)"', bare, re.M)]
+    by_header, constants, owner = {}, {}, {}
+    for path in paths:
+        name = os.path.basename(path)
+        by_header[name], consts = parse_header(_header_text(path))
+        constants.update(consts)
+        for fn in by_header[name]:
+            if owner.setdefault(fn, name) != name:
+                raise PgrError(f"{fn} is declared in {owner[fn]} and again in {name}")
+    return paths, by_header, constants
+
+
+# (pgr.h first, then the products that came with a header of their own, DESIGN.md sections 16-21; PROTOTYPES: what load() binds)
+HEADERS, HEADER_PROTOTYPES, _CONSTANTS = read_abi(HEADER)
+PROTOTYPES = {fn: proto for protos in HEADER_PROTOTYPES.values() for fn, proto in protos.items()}
 globals().update(_CONSTANTS)   # PGR_TERMINATE_BACKWARDS, PGR_SAMPLE_MAJOR, ... PGR_OPT_D2H_REGISTER
 
 _REBUILD = "`python -c 'import __graft_entry__ as g; g.build()'`"
@@ -210,6 +191,13 @@ def _relayout(td, verbose):
     return out
 
 
+def build_dependencies():
+    """The files a library build reads: the one translation unit csrc/pgr_hip.hip, which includes every csrc/*.h (device
+    building blocks, the fan kernel, the host side in pieces), the ABI headers, and the instruction-layout pass."""
+    return [os.path.join(CSRC, "pgr_hip.hip")] + HEADERS + [os.path.join(_HERE, "_isa_layout.py")] + sorted(
+        os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h"))
+
+
 def build(force=False, verbose=False, out=None, extra_flags=()):
     """Compile csrc/pgr_hip.hip (ONE translation unit; it includes every csrc/*.h) for gfx950 (cross-compiles without a GPU): hipcc, then the
     instruction-layout pass over its assembly (_relayout; PGR_NO_RELAYOUT=1 or any failure of that
@@ -221,13 +209,8 @@ def build(force=False, verbose=False, out=None, extra_flags=()):
         raise ValueError("build(extra_flags=...) needs `out`: only the product's own recipe writes the product library")
     LIB_PATH = out or REFERENCE_LIB
     src = os.path.join(CSRC, "pgr_hip.hip")
-    hdr = os.path.join(_HERE, "..", "include", "pgr.h")
-    # (one translation unit: pgr_hip.hip includes every csrc/*.h -- device building blocks, the fan kernel, the host side in pieces)
-    deps = [src, hdr, COHERENT_HEADER, SIGNAL_HEADER, SPECTRUM_HEADER, REFLECTION_HEADER, BEAM_COHERENT_HEADER, BEAM_ARRIVALS_HEADER,
-            os.path.join(_HERE, "_isa_layout.py")] + sorted(
-        os.path.join(CSRC, h) for h in os.listdir(CSRC) if h.endswith(".h"))
     if not force and os.path.exists(LIB_PATH):
-        if os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(d) for d in deps):
+        if os.path.getmtime(LIB_PATH) >= max(os.path.getmtime(d) for d in build_dependencies()):
             return LIB_PATH
     tmp = f"{LIB_PATH}.{os.getpid()}.tmp"   # never leave a half-written library behind
     td = tempfile.mkdtemp(prefix="pgr_build_")
@@ -288,12 +271,12 @@ def load():
                "pygenray_amd._lib.build_contracted()" if ARITH == "contracted" else "") +
             "). pygenray_amd has no CPU fallback.")
     L = ctypes.CDLL(LIB_PATH)
-    for name, (restype, argtypes) in {**PROTOTYPES, **COHERENT_PROTOTYPES, **SIGNAL_PROTOTYPES, **SPECTRUM_PROTOTYPES,
-                                      **REFLECTION_PROTOTYPES, **BEAM_COHERENT_PROTOTYPES, **BEAM_ARRIVALS_PROTOTYPES}.items():
+    for name, (restype, argtypes) in PROTOTYPES.items():
         try:
             fn = getattr(L, name)
         except AttributeError:
-            raise PgrError(f"{LIB_PATH} does not export {name}, which include/pgr.h declares (itself or through pgr_coherent.h / pgr_signal.h / pgr_spectrum.h / pgr_reflection.h / pgr_beam_coherent.h / pgr_beam_arrivals.h): the library is older than "
+            header = next(h for h, protos in HEADER_PROTOTYPES.items() if name in protos)
+            raise PgrError(f"{LIB_PATH} does not export {name}, which include/{header} declares: the library is older than "
                            f"the header. Rebuild it: {_REBUILD}.") from None
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -314,12 +297,137 @@ def _addr(a):
     return None if a is None else a.ctypes.data
 
 
-def _twin(name, weights, upto_p0, rest):
-    """Call tube entry `name(*upto_p0, *rest)` or, with `weights` (a device pointer, not 0 / None), its weighted twin
-    `name`_w, whose one more argument follows p0 (include/pgr.h)."""
-    if weights:
-        return check(getattr(load(), name + "_w")(*upto_p0, weights, *rest))
-    check(getattr(load(), name)(*upto_p0, *rest))
+def _profile(nodes, values, what):
+    """two host sequences, the first or None -> (nodes or None, values) float64, of equal length (`what` words the error)"""
+    v = _c(values).reshape(-1)
+    x = None if nodes is None else _c(nodes).reshape(-1)
+    if x is not None and len(x) != len(v):
+        raise ValueError(f"{what} must have equal length")
+    return x, v
+
+
+class _Fan:
+    """The fan products on raw device pointers (ints), each stated once for both kinds of fan (`_entry` names a kind's entries,
+    `_fan` holds their leading arguments): FanHandle, a device-resident fan, calls pgr_fan_<product>(handle, ...); _Buffers,
+    caller buffers behind a <product>_device function, calls pgr_<product>_device(env, rows, n_rays, n_samples, x, ...), which
+    takes the same arguments after those (include/pgr.h).  The docstrings speak of a FanHandle: S save ranges, M surviving rays."""
+
+    def _call(self, product, *args, suffix=""):
+        check(getattr(load(), self._entry % product + suffix)(*self._fan, *args))
+
+    def _twin(self, product, weights, p0_ptr, *rest):
+        """Tube entry `product` or, with `weights` (a device pointer, not 0 / None), its weighted twin `product`_w, whose one
+        more argument follows p0 (include/pgr.h)."""
+        if weights:
+            return self._call(product, p0_ptr, weights, *rest, suffix="_w")
+        self._call(product, p0_ptr, *rest)
+
+    def boundary_loss(self, tables, out_ptr, nb_ptr=0, ns_ptr=0, stream=0):
+        """pgr_fan_boundary_loss: out[S][M] (device pointer) = the boundary loss in dB of this fan's surviving rays up to
+        every save range; `tables` = boundary_tables(...) (host); nb / ns [S][M] int32 device pointers or 0."""
+        self._call("boundary_loss", *_table_args(tables), out_ptr, nb_ptr, ns_ptr, stream)
+
+    def intensity(self, p0_ptr, depths_ptr, n_depths, out_ptr, stream=0, weights=0):
+        """pgr_fan_intensity on raw device pointers (ints): out[n_depths][S] = the ray-tube intensity of this fan's surviving
+        rays at the receiver depths (include/pgr.h); p0 holds the M surviving rays' launch slowness.  Enqueued on `stream`.
+        `weights` (here and in beam_intensity / arrivals): a device pointer to [S][M] weights of g, which selects the entry's
+        weighted twin (pgr_fan_intensity_w); 0: the unweighted entry."""
+        self._twin("intensity", weights, p0_ptr, depths_ptr, int(n_depths), out_ptr, stream)
+
+    def path_integral(self, a_depths, alpha, out_ptr, stream=0):
+        """pgr_fan_path_integral: out[S][M] (device pointer) = the running path integral of this fan's surviving rays for
+        the absorption profile alpha (dB/m) on the depth nodes a_depths (host sequences; a_depths None with one alpha)."""
+        ad, al = _profile(a_depths, alpha, "a_depths and alpha")
+        self._call("path_integral", _addr(ad), _addr(al), len(al), out_ptr, stream)
+
+    def beam_intensity(self, p0_ptr, bottom_ptr, depths_ptr, n_depths, min_width, out_ptr, stream=0, weights=0):
+        """pgr_fan_beam_intensity on raw device pointers (ints): out[n_depths][S] = the Gaussian-beam intensity of this fan's
+        surviving rays at the receiver depths, bottom[S] the bottom depth at each save range (include/pgr.h)."""
+        self._twin("beam_intensity", weights, p0_ptr, bottom_ptr, depths_ptr, int(n_depths), float(min_width), out_ptr, stream)
+
+    def arrival_counts(self, p0_ptr, depths_ptr, n_depths, cols, counts_ptr, stream=0):
+        """pgr_fan_arrival_counts: counts[n_depths][len(cols)] (int64, device pointer) = the arrivals of this fan's surviving
+        rays at each receiver depth and requested column; `cols` is a host sequence of column indices (include/pgr.h)."""
+        c = np.ascontiguousarray(cols, dtype=np.int32)
+        self._call("arrival_counts", p0_ptr, depths_ptr, int(n_depths), _addr(c), len(c), counts_ptr, stream)
+
+    def arrivals(self, p0_ptr, depths_ptr, n_depths, cols, offsets_ptr, n_arrivals, tube_ptr, w_ptr, t_ptr, p_ptr, i_ptr,
+                 stream=0, weights=0):
+        """pgr_fan_arrivals: the arrivals themselves, written from offsets[j * len(cols) + c] into tube (int32) / w / T / p /
+        I (device pointers holding n_arrivals each)."""
+        c = np.ascontiguousarray(cols, dtype=np.int32)
+        self._twin("arrivals", weights, p0_ptr, depths_ptr, int(n_depths), _addr(c), len(c), offsets_ptr, int(n_arrivals),
+                   tube_ptr, w_ptr, t_ptr, p_ptr, i_ptr, stream)
+
+    def travel_time_kernel(self, ranges_ptr, n_ranges, depths_ptr, n_depths, column, out_ptr, stream=0):
+        """pgr_fan_travel_time_kernel on raw device pointers (ints): out[M][n_ranges][n_depths] = the travel-time sensitivity
+        kernel of this fan's surviving rays at save column `column` on the grid ranges x depths (include/pgr.h)."""
+        self._call("travel_time_kernel", ranges_ptr, int(n_ranges), depths_ptr, int(n_depths), int(column), out_ptr, stream)
+
+    def time_front(self, cols, t_ptr, z_ptr, p_ptr, turns_ptr, stream=0):
+        """pgr_fan_time_front on raw device pointers (ints; 0 / None: not wanted): t / z / p [len(cols)][M] float64 = the
+        surviving rays' samples at the save columns `cols` (a host sequence of column indices), turns [len(cols)][M] int32
+        = their turning-point counts up to those columns (include/pgr.h).  Enqueued on `stream`."""
+        c = None if cols is None else np.ascontiguousarray(cols, dtype=np.int32)
+        self._call("time_front", _addr(c), 0 if c is None else len(c), t_ptr, z_ptr, p_ptr, turns_ptr, stream)
+
+    def caustic_index(self, nb_ptr, ns_ptr, kappa_ptr, stream=0):
+        """pgr_fan_caustic_index on raw device pointers (ints): kappa[S][M] int32 = the caustics every tube of this fan's
+        surviving rays has passed up to every save range; nb / ns [S][M] int32, the per-sample bounce counts boundary_loss
+        writes, or 0 (a fan without bounces).  Enqueued on `stream`."""
+        self._call("caustic_index", nb_ptr or None, ns_ptr or None, kappa_ptr, stream)
+
+    def pressure(self, p0_ptr, q_ptr, frequency, depths_ptr, n_depths, re_ptr, im_ptr, stream=0, weights=0):
+        """pgr_fan_pressure_w on raw device pointers (ints): re / im [n_depths][S] = the coherent sum of this fan's ray tubes
+        at the receiver depths; q [S][M] int32 the tubes' phase index in quarter cycles or 0, `weights` as in ``intensity``
+        or 0 (include/pgr.h)."""
+        self._call("pressure", p0_ptr, weights or None, q_ptr or None, float(frequency), depths_ptr, int(n_depths), re_ptr, im_ptr,
+                   stream, suffix="_w")
+
+    def pressure_phi(self, p0_ptr, q_ptr, phi_ptr, frequency, depths_ptr, n_depths, re_ptr, im_ptr, stream=0, weights=0):
+        """pgr_fan_pressure_phi on raw device pointers (ints): ``pressure`` with phi [S][M] float64, the lag in cycles every
+        surviving ray has collected up to every save range (include/pgr_reflection.h); phi 0 is refused."""
+        self._call("pressure", p0_ptr, weights or None, q_ptr or None, phi_ptr or None, float(frequency), depths_ptr,
+                   int(n_depths), re_ptr, im_ptr, stream, suffix="_phi")
+
+    def beam_pressure(self, p0_ptr, q_ptr, frequency, bottom_ptr, depths_ptr, n_depths, min_width, curvature, re_ptr, im_ptr,
+                      stream=0, weights=0):
+        """pgr_fan_beam_pressure_w on raw device pointers (ints): re / im [n_depths][S] = the coherent sum of this fan's
+        Gaussian beams at the receiver depths; q and `weights` as in ``pressure``, bottom and min_width as in
+        ``beam_intensity``, `curvature` false for the plain geometric beam (include/pgr_beam_coherent.h)."""
+        self._call("beam_pressure", p0_ptr, weights or None, q_ptr or None, float(frequency), bottom_ptr, depths_ptr,
+                   int(n_depths), float(min_width), int(bool(curvature)), re_ptr, im_ptr, stream, suffix="_w")
+
+    def beam_arrival_counts(self, p0_ptr, q_ptr, bottom_ptr, depths_ptr, n_depths, min_width, cols, counts_ptr, stream=0,
+                            weights=0):
+        """pgr_fan_beam_arrival_counts_w on raw device pointers (ints): counts[n_depths][len(cols)] (int64) = the terms
+        ``beam_pressure`` adds at each receiver depth and requested column; `cols` a host sequence of column indices, the
+        other arguments ``beam_pressure``'s (include/pgr_beam_arrivals.h)."""
+        c = np.ascontiguousarray(cols, dtype=np.int32)
+        self._call("beam_arrival_counts", p0_ptr, weights or None, q_ptr or None, bottom_ptr, depths_ptr, int(n_depths),
+                   float(min_width), _addr(c), len(c), counts_ptr, stream, suffix="_w")
+
+    def beam_arrivals(self, p0_ptr, q_ptr, bottom_ptr, depths_ptr, n_depths, min_width, cols, curvature, offsets_ptr, n_arrivals,
+                      tube_ptr, image_ptr, time_ptr, amp_ptr, qa_ptr, stream=0, weights=0):
+        """pgr_fan_beam_arrivals_w: those terms themselves, written from offsets[j * len(cols) + c] into tube, image, qa
+        (int32) and time, amplitude (float64), device pointers holding n_arrivals each."""
+        c = np.ascontiguousarray(cols, dtype=np.int32)
+        self._call("beam_arrivals", p0_ptr, weights or None, q_ptr or None, bottom_ptr, depths_ptr, int(n_depths),
+                   float(min_width), _addr(c), len(c), int(bool(curvature)), offsets_ptr, int(n_arrivals), tube_ptr, image_ptr,
+                   time_ptr, amp_ptr, qa_ptr, stream, suffix="_w")
+
+
+class _Buffers(_Fan):
+    """caller buffers as a fan: `fan` are the leading arguments of the one buffer entry the <product>_device function calls"""
+    _entry = "pgr_%s_device"
+
+    def __init__(self, *fan):
+        self._fan = fan
+
+
+def _buffers(env, n_rays, n_samples, x_ptr, *rows):
+    """_Buffers of the rows of T / z / p [n_samples][n_rays] an entry reads on the save ranges x of the frame of `env`"""
+    return _Buffers(env._h, *rows, int(n_rays), int(n_samples), x_ptr)
 
 
 class EnvHandle:
@@ -485,9 +593,11 @@ class EnvHandle:
         return out
 
 
-class FanHandle:
+class FanHandle(_Fan):
     """A fan whose results stay in HBM (pgr_fan_*, include/pgr.h): launched in the constructor (returns while the
-    kernel runs), per-ray arrays and trajectories fetched on demand."""
+    kernel runs), per-ray arrays and trajectories fetched on demand, the products of _Fan computed where it is."""
+    _entry = "pgr_fan_%s"
+    _fan = property(lambda self: (self._h,))
 
     def __init__(self, env, x0, x1, S, y0=None, ode_angles_deg=None, source_depth=0.0, c_source=1.0, rtol=1e-9,
                  atol=1e-6, terminate_backwards=True, max_steps=1_000_000, stored_sign=False, exact_samples=False,
@@ -531,11 +641,6 @@ class FanHandle:
         k = np.empty((self.K, self.M), np.int8)
         check(load().pgr_fan_fetch_bounces(self._h, _addr(x), _addr(p), _addr(k)))
         return x, p, k
-
-    def boundary_loss(self, tables, out_ptr, nb_ptr=0, ns_ptr=0, stream=0):
-        """pgr_fan_boundary_loss: out[S][M] (device pointer) = the boundary loss in dB of this fan's surviving rays up to
-        every save range; `tables` = boundary_tables(...) (host); nb / ns [S][M] int32 device pointers or 0."""
-        check(load().pgr_fan_boundary_loss(self._h, *_table_args(tables), out_ptr, nb_ptr, ns_ptr, stream))
 
     def wait(self):
         n, m = ctypes.c_int64(0), ctypes.c_int64(0)
@@ -581,103 +686,6 @@ class FanHandle:
                                            PGR_COMPACT if compact else 0))
         return {k: (v.reshape(-1)[:self.S * cols].reshape(self.S, cols) if cols != self.N else v)
                 for k, v in bufs.items() if v is not None}
-
-    def intensity(self, p0_ptr, depths_ptr, n_depths, out_ptr, stream=0, weights=0):
-        """pgr_fan_intensity on raw device pointers (ints): out[n_depths][S] = the ray-tube intensity of this fan's surviving
-        rays at the receiver depths (include/pgr.h); p0 holds the M surviving rays' launch slowness.  Enqueued on `stream`.
-        `weights` (here and in beam_intensity / arrivals): a device pointer to [S][M] weights of g, which selects the entry's
-        weighted twin (pgr_fan_intensity_w); 0: the unweighted entry."""
-        _twin("pgr_fan_intensity", weights, (self._h, p0_ptr), (depths_ptr, int(n_depths), out_ptr, stream))
-
-    def path_integral(self, a_depths, alpha, out_ptr, stream=0):
-        """pgr_fan_path_integral: out[S][M] (device pointer) = the running path integral of this fan's surviving rays for
-        the absorption profile alpha (dB/m) on the depth nodes a_depths (host sequences; a_depths None with one alpha)."""
-        al = _c(alpha).reshape(-1)
-        ad = None if a_depths is None else _c(a_depths).reshape(-1)
-        if ad is not None and len(ad) != len(al):
-            raise ValueError("a_depths and alpha must have equal length")
-        check(load().pgr_fan_path_integral(self._h, _addr(ad), _addr(al), len(al), out_ptr, stream))
-
-    def beam_intensity(self, p0_ptr, bottom_ptr, depths_ptr, n_depths, min_width, out_ptr, stream=0, weights=0):
-        """pgr_fan_beam_intensity on raw device pointers (ints): out[n_depths][S] = the Gaussian-beam intensity of this fan's
-        surviving rays at the receiver depths, bottom[S] the bottom depth at each save range (include/pgr.h)."""
-        _twin("pgr_fan_beam_intensity", weights, (self._h, p0_ptr),
-              (bottom_ptr, depths_ptr, int(n_depths), float(min_width), out_ptr, stream))
-
-    def arrival_counts(self, p0_ptr, depths_ptr, n_depths, cols, counts_ptr, stream=0):
-        """pgr_fan_arrival_counts: counts[n_depths][len(cols)] (int64, device pointer) = the arrivals of this fan's surviving
-        rays at each receiver depth and requested column; `cols` is a host sequence of column indices (include/pgr.h)."""
-        c = np.ascontiguousarray(cols, dtype=np.int32)
-        check(load().pgr_fan_arrival_counts(self._h, p0_ptr, depths_ptr, int(n_depths), _addr(c), len(c), counts_ptr, stream))
-
-    def arrivals(self, p0_ptr, depths_ptr, n_depths, cols, offsets_ptr, n_arrivals, tube_ptr, w_ptr, t_ptr, p_ptr, i_ptr,
-                 stream=0, weights=0):
-        """pgr_fan_arrivals: the arrivals themselves, written from offsets[j * len(cols) + c] into tube (int32) / w / T / p /
-        I (device pointers holding n_arrivals each)."""
-        c = np.ascontiguousarray(cols, dtype=np.int32)
-        _twin("pgr_fan_arrivals", weights, (self._h, p0_ptr),
-              (depths_ptr, int(n_depths), _addr(c), len(c), offsets_ptr, int(n_arrivals), tube_ptr, w_ptr, t_ptr, p_ptr, i_ptr,
-               stream))
-
-    def travel_time_kernel(self, ranges_ptr, n_ranges, depths_ptr, n_depths, column, out_ptr, stream=0):
-        """pgr_fan_travel_time_kernel on raw device pointers (ints): out[M][n_ranges][n_depths] = the travel-time sensitivity
-        kernel of this fan's surviving rays at save column `column` on the grid ranges x depths (include/pgr.h)."""
-        check(load().pgr_fan_travel_time_kernel(self._h, ranges_ptr, int(n_ranges), depths_ptr, int(n_depths), int(column),
-                                                out_ptr, stream))
-
-    def time_front(self, cols, t_ptr, z_ptr, p_ptr, turns_ptr, stream=0):
-        """pgr_fan_time_front on raw device pointers (ints; 0 / None: not wanted): t / z / p [len(cols)][M] float64 = the
-        surviving rays' samples at the save columns `cols` (a host sequence of column indices), turns [len(cols)][M] int32
-        = their turning-point counts up to those columns (include/pgr.h).  Enqueued on `stream`."""
-        c = None if cols is None else np.ascontiguousarray(cols, dtype=np.int32)
-        check(load().pgr_fan_time_front(self._h, _addr(c), 0 if c is None else len(c), t_ptr, z_ptr, p_ptr, turns_ptr, stream))
-
-    def caustic_index(self, nb_ptr, ns_ptr, kappa_ptr, stream=0):
-        """pgr_fan_caustic_index on raw device pointers (ints): kappa[S][M] int32 = the caustics every tube of this fan's
-        surviving rays has passed up to every save range; nb / ns [S][M] int32, the per-sample bounce counts boundary_loss
-        writes, or 0 (a fan without bounces).  Enqueued on `stream`."""
-        check(load().pgr_fan_caustic_index(self._h, nb_ptr, ns_ptr, kappa_ptr, stream))
-
-    def pressure(self, p0_ptr, q_ptr, frequency, depths_ptr, n_depths, re_ptr, im_ptr, stream=0, weights=0):
-        """pgr_fan_pressure_w on raw device pointers (ints): re / im [n_depths][S] = the coherent sum of this fan's ray tubes
-        at the receiver depths; q [S][M] int32 the tubes' phase index in quarter cycles or 0, `weights` as in ``intensity``
-        or 0 (include/pgr.h)."""
-        check(load().pgr_fan_pressure_w(self._h, p0_ptr, weights or None, q_ptr or None, float(frequency), depths_ptr,
-                                        int(n_depths), re_ptr, im_ptr, stream))
-
-    def pressure_phi(self, p0_ptr, q_ptr, phi_ptr, frequency, depths_ptr, n_depths, re_ptr, im_ptr, stream=0, weights=0):
-        """pgr_fan_pressure_phi on raw device pointers (ints): ``pressure`` with phi [S][M] float64, the lag in cycles every
-        surviving ray has collected up to every save range (include/pgr_reflection.h); phi 0 is refused."""
-        check(load().pgr_fan_pressure_phi(self._h, p0_ptr, weights or None, q_ptr or None, phi_ptr or None, float(frequency),
-                                          depths_ptr, int(n_depths), re_ptr, im_ptr, stream))
-
-    def beam_pressure(self, p0_ptr, q_ptr, frequency, bottom_ptr, depths_ptr, n_depths, min_width, curvature, re_ptr, im_ptr,
-                      stream=0, weights=0):
-        """pgr_fan_beam_pressure_w on raw device pointers (ints): re / im [n_depths][S] = the coherent sum of this fan's
-        Gaussian beams at the receiver depths; q and `weights` as in ``pressure``, bottom and min_width as in
-        ``beam_intensity``, `curvature` false for the plain geometric beam (include/pgr_beam_coherent.h)."""
-        check(load().pgr_fan_beam_pressure_w(self._h, p0_ptr, weights or None, q_ptr or None, float(frequency), bottom_ptr,
-                                             depths_ptr, int(n_depths), float(min_width), int(bool(curvature)), re_ptr, im_ptr,
-                                             stream))
-
-    def beam_arrival_counts(self, p0_ptr, q_ptr, bottom_ptr, depths_ptr, n_depths, min_width, cols, counts_ptr, stream=0,
-                            weights=0):
-        """pgr_fan_beam_arrival_counts_w on raw device pointers (ints): counts[n_depths][len(cols)] (int64) = the terms
-        ``beam_pressure`` adds at each receiver depth and requested column; `cols` a host sequence of column indices, the
-        other arguments ``beam_pressure``'s (include/pgr_beam_arrivals.h)."""
-        c = np.ascontiguousarray(cols, dtype=np.int32)
-        check(load().pgr_fan_beam_arrival_counts_w(self._h, p0_ptr, weights or None, q_ptr or None, bottom_ptr, depths_ptr,
-                                                   int(n_depths), float(min_width), _addr(c), len(c), counts_ptr, stream))
-
-    def beam_arrivals(self, p0_ptr, q_ptr, bottom_ptr, depths_ptr, n_depths, min_width, cols, curvature, offsets_ptr, n_arrivals,
-                      tube_ptr, image_ptr, time_ptr, amp_ptr, qa_ptr, stream=0, weights=0):
-        """pgr_fan_beam_arrivals_w: those terms themselves, written from offsets[j * len(cols) + c] into tube, image, qa
-        (int32) and time, amplitude (float64), device pointers holding n_arrivals each."""
-        c = np.ascontiguousarray(cols, dtype=np.int32)
-        check(load().pgr_fan_beam_arrivals_w(self._h, p0_ptr, weights or None, q_ptr or None, bottom_ptr, depths_ptr,
-                                             int(n_depths), float(min_width), _addr(c), len(c), int(bool(curvature)),
-                                             offsets_ptr, int(n_arrivals), tube_ptr, image_ptr, time_ptr, amp_ptr, qa_ptr,
-                                             stream))
 
     def close(self):
         if getattr(self, "_h", None):
@@ -760,43 +768,38 @@ def intensity_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, depths
     (stored sign convention) on `env` (an EnvHandle); see include/pgr.h.  `weights` (here and in beam_intensity_device /
     arrivals_device): a device pointer to [n_samples][n_rays] weights of g, which selects the entry's weighted twin
     (pgr_intensity_device_w); 0: the unweighted entry."""
-    _twin("pgr_intensity_device", weights, (env._h, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr),
-          (depths_ptr, int(n_depths), out_ptr, stream))
+    _buffers(env, n_rays, n_samples, x_ptr, z_ptr, p_ptr).intensity(p0_ptr, depths_ptr, n_depths, out_ptr, stream, weights)
 
 
 def beam_intensity_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, bottom_ptr, depths_ptr, n_depths, min_width,
                           out_ptr, stream=0, weights=0):
     """pgr_beam_intensity_device on raw device pointers (ints): the Gaussian-beam intensity of caller buffers z / p
     [n_samples][n_rays] (stored sign convention) on `env` (an EnvHandle); see include/pgr.h."""
-    _twin("pgr_beam_intensity_device", weights, (env._h, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr),
-          (bottom_ptr, depths_ptr, int(n_depths), float(min_width), out_ptr, stream))
+    _buffers(env, n_rays, n_samples, x_ptr, z_ptr, p_ptr).beam_intensity(p0_ptr, bottom_ptr, depths_ptr, n_depths, min_width,
+                                                                         out_ptr, stream, weights)
 
 
 def arrival_counts_device(env, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, depths_ptr, n_depths, cols, counts_ptr,
                           stream=0):
     """pgr_arrival_counts_device on raw device pointers (ints) of caller buffers z / p [n_samples][n_rays] (stored sign
     convention) on `env` (an EnvHandle); `cols` a host sequence of column indices; see include/pgr.h."""
-    c = np.ascontiguousarray(cols, dtype=np.int32)
-    check(load().pgr_arrival_counts_device(env._h, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr, depths_ptr,
-                                           int(n_depths), _addr(c), len(c), counts_ptr, stream))
+    _buffers(env, n_rays, n_samples, x_ptr, z_ptr, p_ptr).arrival_counts(p0_ptr, depths_ptr, n_depths, cols, counts_ptr, stream)
 
 
 def arrivals_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, depths_ptr, n_depths, cols, offsets_ptr,
                     n_arrivals, tube_ptr, w_ptr, t_out_ptr, p_out_ptr, i_ptr, stream=0, weights=0):
     """pgr_arrivals_device on raw device pointers (ints): arrival_counts_device's walk, writing the arrivals; see
     include/pgr.h."""
-    c = np.ascontiguousarray(cols, dtype=np.int32)
-    _twin("pgr_arrivals_device", weights, (env._h, t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr),
-          (depths_ptr, int(n_depths), _addr(c), len(c), offsets_ptr, int(n_arrivals), tube_ptr, w_ptr, t_out_ptr, p_out_ptr,
-           i_ptr, stream))
+    _buffers(env, n_rays, n_samples, x_ptr, t_ptr, z_ptr, p_ptr).arrivals(
+        p0_ptr, depths_ptr, n_depths, cols, offsets_ptr, n_arrivals, tube_ptr, w_ptr, t_out_ptr, p_out_ptr, i_ptr, stream, weights)
 
 
 def travel_time_kernel_device(env, t_ptr, z_ptr, n_rays, n_samples, x_ptr, ranges_ptr, n_ranges, depths_ptr, n_depths,
                               column, out_ptr, stream=0):
     """pgr_travel_time_kernel_device on raw device pointers (ints): the travel-time sensitivity kernel of caller buffers
     T / z [n_samples][n_rays] (stored sign convention) on `env` (an EnvHandle); see include/pgr.h."""
-    check(load().pgr_travel_time_kernel_device(env._h, t_ptr, z_ptr, int(n_rays), int(n_samples), x_ptr, ranges_ptr,
-                                               int(n_ranges), depths_ptr, int(n_depths), int(column), out_ptr, stream))
+    _buffers(env, n_rays, n_samples, x_ptr, t_ptr, z_ptr).travel_time_kernel(ranges_ptr, n_ranges, depths_ptr, n_depths, column,
+                                                                             out_ptr, stream)
 
 
 def time_front_device(device, t_ptr, z_ptr, p_ptr, n_rays, n_samples, cols, t_out_ptr, z_out_ptr, p_out_ptr, turns_ptr,
@@ -804,34 +807,21 @@ def time_front_device(device, t_ptr, z_ptr, p_ptr, n_rays, n_samples, cols, t_ou
     """pgr_time_front_device on raw device pointers (ints; 0 / None: absent): the samples at the save columns `cols` (a
     host sequence, or None for a NULL list) and the turning-point counts up to them, of caller buffers T / z / p
     [n_samples][n_rays] on `device`; see include/pgr.h."""
-    c = None if cols is None else np.ascontiguousarray(cols, dtype=np.int32)
-    check(load().pgr_time_front_device(int(device), t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples), _addr(c),
-                                       0 if c is None else len(c), t_out_ptr, z_out_ptr, p_out_ptr, turns_ptr, stream))
+    _Buffers(int(device), t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples)).time_front(cols, t_out_ptr, z_out_ptr, p_out_ptr,
+                                                                                     turns_ptr, stream)
 
 
 def path_integral_device(env, t_ptr, z_ptr, n_rays, n_samples, x_ptr, a_depths, alpha, out_ptr, stream=0):
     """pgr_path_integral_device on raw device pointers (ints): out[n_samples][n_rays] = the running path integral of caller
     buffers T / z [n_samples][n_rays] (stored sign convention) on `env` (an EnvHandle) for the absorption profile alpha
     (dB/m) on the depth nodes a_depths (host sequences; a_depths None with one alpha); see include/pgr.h."""
-    al = _c(alpha).reshape(-1)
-    ad = None if a_depths is None else _c(a_depths).reshape(-1)
-    if ad is not None and len(ad) != len(al):
-        raise ValueError("a_depths and alpha must have equal length")
-    check(load().pgr_path_integral_device(env._h, t_ptr, z_ptr, int(n_rays), int(n_samples), x_ptr, _addr(ad),
-                                          _addr(al), len(al), out_ptr, stream))
+    _buffers(env, n_rays, n_samples, x_ptr, t_ptr, z_ptr).path_integral(a_depths, alpha, out_ptr, stream)
 
 
 def boundary_tables(bottom, surface, beta):
     """Three (nodes or None, values) pairs -> the host arrays pgr_fan_boundary_loss / pgr_boundary_loss_device take (kept
     alive by the returned tuple): the bottom loss on grazing angles, the surface loss, the bottom slope in degrees on ranges."""
-    out = []
-    for nodes, values in (bottom, surface, beta):
-        v = _c(values).reshape(-1)
-        x = None if nodes is None else _c(nodes).reshape(-1)
-        if x is not None and len(x) != len(v):
-            raise ValueError("a table's nodes and values must have equal length")
-        out.append((x, v))
-    return tuple(out)
+    return tuple(_profile(nodes, values, "a table's nodes and values") for nodes, values in (bottom, surface, beta))
 
 
 def _table_args(tables):
@@ -845,8 +835,8 @@ def boundary_loss_device(env, bx_ptr, bp_ptr, bk_ptr, n_rays, K, x0, x1, n_sampl
                          stream=0):
     """pgr_boundary_loss_device on raw device pointers (ints): the log bx, bp (float64) and bk (int8), [K][n_rays] each, stored
     sign, on the save ranges np.linspace(x0, x1, n_samples) of the frame of `env`."""
-    check(load().pgr_boundary_loss_device(env._h, bx_ptr, bp_ptr, bk_ptr, int(n_rays), int(K), float(x0), float(x1),
-                                          int(n_samples), *_table_args(tables), out_ptr, nb_ptr, ns_ptr, stream))
+    _Buffers(env._h, bx_ptr, bp_ptr, bk_ptr, int(n_rays), int(K), float(x0), float(x1), int(n_samples)).boundary_loss(
+        tables, out_ptr, nb_ptr, ns_ptr, stream)
 
 
 def absorption_weights_device(device, a_ptr, n, w_ptr, stream=0):
@@ -858,35 +848,31 @@ def absorption_weights_device(device, a_ptr, n, w_ptr, stream=0):
 def caustic_index_device(device, z_ptr, n_rays, n_samples, nb_ptr, ns_ptr, kappa_ptr, stream=0):
     """pgr_caustic_index_device on raw device pointers (ints; nb / ns 0: absent): kappa[n_samples][n_rays] int32 of caller rows
     z [n_samples][n_rays] (stored sign convention) on `device`; see include/pgr.h."""
-    check(load().pgr_caustic_index_device(int(device), z_ptr, int(n_rays), int(n_samples), nb_ptr or None, ns_ptr or None,
-                                          kappa_ptr, stream))
+    _Buffers(int(device), z_ptr, int(n_rays), int(n_samples)).caustic_index(nb_ptr, ns_ptr, kappa_ptr, stream)
 
 
 def pressure_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, q_ptr, frequency, depths_ptr, n_depths, re_ptr,
                     im_ptr, stream=0, weights=0):
     """pgr_pressure_device_w on raw device pointers (ints; q / weights 0: absent): the coherent tube sum of caller buffers
     T / z / p [n_samples][n_rays] (stored sign convention) on `env` (an EnvHandle); see include/pgr.h."""
-    check(load().pgr_pressure_device_w(env._h, t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr,
-                                       weights or None, q_ptr or None, float(frequency), depths_ptr, int(n_depths), re_ptr,
-                                       im_ptr, stream))
+    _buffers(env, n_rays, n_samples, x_ptr, t_ptr, z_ptr, p_ptr).pressure(p0_ptr, q_ptr, frequency, depths_ptr, n_depths, re_ptr,
+                                                                          im_ptr, stream, weights)
 
 
 def pressure_phi_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, q_ptr, phi_ptr, frequency, depths_ptr,
                         n_depths, re_ptr, im_ptr, stream=0, weights=0):
     """pgr_pressure_device_phi on raw device pointers (ints): ``pressure_device`` with phi [n_samples][n_rays] float64, the
     rays' lag in cycles (include/pgr_reflection.h); phi 0 is refused."""
-    check(load().pgr_pressure_device_phi(env._h, t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr,
-                                         weights or None, q_ptr or None, phi_ptr or None, float(frequency), depths_ptr,
-                                         int(n_depths), re_ptr, im_ptr, stream))
+    _buffers(env, n_rays, n_samples, x_ptr, t_ptr, z_ptr, p_ptr).pressure_phi(p0_ptr, q_ptr, phi_ptr, frequency, depths_ptr,
+                                                                              n_depths, re_ptr, im_ptr, stream, weights)
 
 
 def beam_pressure_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, q_ptr, frequency, bottom_ptr, depths_ptr,
                          n_depths, min_width, curvature, re_ptr, im_ptr, stream=0, weights=0):
     """pgr_beam_pressure_device_w on raw device pointers (ints; q / weights 0: absent): the coherent Gaussian-beam sum of caller
     buffers T / z / p [n_samples][n_rays] (stored sign convention) on `env` (an EnvHandle); see include/pgr_beam_coherent.h."""
-    check(load().pgr_beam_pressure_device_w(env._h, t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr,
-                                            weights or None, q_ptr or None, float(frequency), bottom_ptr, depths_ptr,
-                                            int(n_depths), float(min_width), int(bool(curvature)), re_ptr, im_ptr, stream))
+    _buffers(env, n_rays, n_samples, x_ptr, t_ptr, z_ptr, p_ptr).beam_pressure(
+        p0_ptr, q_ptr, frequency, bottom_ptr, depths_ptr, n_depths, min_width, curvature, re_ptr, im_ptr, stream, weights)
 
 
 def beam_arrival_counts_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, q_ptr, bottom_ptr, depths_ptr,
@@ -894,10 +880,8 @@ def beam_arrival_counts_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_pt
     """pgr_beam_arrival_counts_device_w on raw device pointers (ints; q / weights 0: absent): the terms ``beam_pressure_device``
     adds per receiver depth and requested column of `cols` (a host sequence), of caller buffers T / z / p [n_samples][n_rays]
     (stored sign convention) on `env` (an EnvHandle); see include/pgr_beam_arrivals.h."""
-    c = np.ascontiguousarray(cols, dtype=np.int32)
-    check(load().pgr_beam_arrival_counts_device_w(env._h, t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr,
-                                                  weights or None, q_ptr or None, bottom_ptr, depths_ptr, int(n_depths),
-                                                  float(min_width), _addr(c), len(c), counts_ptr, stream))
+    _buffers(env, n_rays, n_samples, x_ptr, t_ptr, z_ptr, p_ptr).beam_arrival_counts(
+        p0_ptr, q_ptr, bottom_ptr, depths_ptr, n_depths, min_width, cols, counts_ptr, stream, weights)
 
 
 def beam_arrivals_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_ptr, q_ptr, bottom_ptr, depths_ptr, n_depths,
@@ -905,11 +889,17 @@ def beam_arrivals_device(env, t_ptr, z_ptr, p_ptr, n_rays, n_samples, x_ptr, p0_
                          stream=0, weights=0):
     """pgr_beam_arrivals_device_w on raw device pointers (ints): beam_arrival_counts_device's walk, writing the arrivals; see
     include/pgr_beam_arrivals.h."""
-    c = np.ascontiguousarray(cols, dtype=np.int32)
-    check(load().pgr_beam_arrivals_device_w(env._h, t_ptr, z_ptr, p_ptr, int(n_rays), int(n_samples), x_ptr, p0_ptr,
-                                            weights or None, q_ptr or None, bottom_ptr, depths_ptr, int(n_depths),
-                                            float(min_width), _addr(c), len(c), int(bool(curvature)), offsets_ptr,
-                                            int(n_arrivals), tube_ptr, image_ptr, time_ptr, amp_ptr, qa_ptr, stream))
+    _buffers(env, n_rays, n_samples, x_ptr, t_ptr, z_ptr, p_ptr).beam_arrivals(
+        p0_ptr, q_ptr, bottom_ptr, depths_ptr, n_depths, min_width, cols, curvature, offsets_ptr, n_arrivals, tube_ptr, image_ptr,
+        time_ptr, amp_ptr, qa_ptr, stream, weights)
+
+
+def _signal(suffix, device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, phi, tstart_ptr, frequency, inv_sigma, dt, n_times,
+            re_ptr, im_ptr, stream):
+    """pgr_signal_device`suffix`; `phi`: the pointers the entry takes between q and tstart: () or (phi_ptr,)"""
+    check(getattr(load(), "pgr_signal_device" + suffix)(
+        int(device), offsets_ptr, int(n_groups), t_ptr, i_ptr, q_ptr or None, *(p or None for p in phi), tstart_ptr,
+        float(frequency), float(inv_sigma), float(dt), int(n_times), re_ptr, im_ptr, stream))
 
 
 def signal_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, tstart_ptr, frequency, inv_sigma, dt, n_times, re_ptr,
@@ -917,17 +907,25 @@ def signal_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, tstart_ptr
     """pgr_signal_device on raw device pointers (ints; q 0: absent): re / im [n_groups][n_times] = the complex baseband signal
     of a Gaussian pulse (inv_sigma = 1 / sigma; 0: CW) summed over the arrivals T / I / q of each group [offsets[g],
     offsets[g + 1]) at the times tstart[g] + n dt; see include/pgr_signal.h."""
-    check(load().pgr_signal_device(int(device), offsets_ptr, int(n_groups), t_ptr, i_ptr, q_ptr or None, tstart_ptr,
-                                   float(frequency), float(inv_sigma), float(dt), int(n_times), re_ptr, im_ptr, stream))
+    _signal("", device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, (), tstart_ptr, frequency, inv_sigma, dt, n_times, re_ptr,
+            im_ptr, stream)
 
 
 def signal_phi_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, phi_ptr, tstart_ptr, frequency, inv_sigma, dt, n_times,
                       re_ptr, im_ptr, stream=0):
     """pgr_signal_device_phi on raw device pointers (ints): ``signal_device`` with phi float64, every arrival's lag in cycles
     (include/pgr_reflection.h); phi 0 is refused."""
-    check(load().pgr_signal_device_phi(int(device), offsets_ptr, int(n_groups), t_ptr, i_ptr, q_ptr or None, phi_ptr or None,
-                                       tstart_ptr, float(frequency), float(inv_sigma), float(dt), int(n_times), re_ptr, im_ptr,
-                                       stream))
+    _signal("_phi", device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, (phi_ptr,), tstart_ptr, frequency, inv_sigma, dt, n_times,
+            re_ptr, im_ptr, stream)
+
+
+def _spectrum(suffix, device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, phi, l_ptr, tred_ptr, freq, alpha, re_ptr, im_ptr,
+              stream):
+    """pgr_spectrum_device`suffix`; `phi`: the pointers the entry takes between q and l: () or (phi_ptr,)"""
+    al, fr = _profile(alpha, freq, "freq and alpha")
+    check(getattr(load(), "pgr_spectrum_device" + suffix)(
+        int(device), offsets_ptr, int(n_groups), t_ptr, i_ptr, q_ptr or None, *(p or None for p in phi), l_ptr or None, tred_ptr,
+        _addr(fr), _addr(al), len(fr), re_ptr, im_ptr, stream))
 
 
 def spectrum_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, l_ptr, tred_ptr, freq, alpha, re_ptr, im_ptr,
@@ -935,21 +933,12 @@ def spectrum_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, l_ptr, t
     """pgr_spectrum_device on raw device pointers (ints; q / l 0: absent) and the HOST sequences freq (Hz) and alpha (dB per
     metre, or None; given exactly when l is): re / im [n_groups][len(freq)] = the transfer function of the arrivals T / I / q
     / L of each group [offsets[g], offsets[g + 1]) at every frequency, reduced by tred[g]; see include/pgr_spectrum.h."""
-    fr = _c(freq).reshape(-1)
-    al = None if alpha is None else _c(alpha).reshape(-1)
-    if al is not None and len(al) != len(fr):
-        raise ValueError("freq and alpha must have equal length")
-    check(load().pgr_spectrum_device(int(device), offsets_ptr, int(n_groups), t_ptr, i_ptr, q_ptr or None, l_ptr or None,
-                                     tred_ptr, _addr(fr), _addr(al), len(fr), re_ptr, im_ptr, stream))
+    _spectrum("", device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, (), l_ptr, tred_ptr, freq, alpha, re_ptr, im_ptr, stream)
 
 
 def spectrum_phi_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, phi_ptr, l_ptr, tred_ptr, freq, alpha, re_ptr, im_ptr,
                         stream=0):
     """pgr_spectrum_device_phi on raw device pointers (ints) and the HOST sequences freq and alpha: ``spectrum_device`` with phi
     float64, every arrival's lag in cycles (include/pgr_reflection.h); phi 0 is refused."""
-    fr = _c(freq).reshape(-1)
-    al = None if alpha is None else _c(alpha).reshape(-1)
-    if al is not None and len(al) != len(fr):
-        raise ValueError("freq and alpha must have equal length")
-    check(load().pgr_spectrum_device_phi(int(device), offsets_ptr, int(n_groups), t_ptr, i_ptr, q_ptr or None, phi_ptr or None,
-                                         l_ptr or None, tred_ptr, _addr(fr), _addr(al), len(fr), re_ptr, im_ptr, stream))
+    _spectrum("_phi", device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, (phi_ptr,), l_ptr, tred_ptr, freq, alpha, re_ptr, im_ptr,
+              stream)

@@ -9,7 +9,7 @@ fan, uploaded through torch for a host fan.  There is no CPU path.  ``transmissi
 import numpy as np
 
 from .ray_objects import _columns
-from .transmission import _TracedFan, _absorption_profile, _check_flatearth, _save_grid
+from ._fan_frame import _TracedFan, _absorption_profile, _check_flatearth, _save_grid
 
 
 def thorp_absorption(frequency_hz):

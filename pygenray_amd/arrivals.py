@@ -7,7 +7,8 @@ already are -- in HBM for a device-resident fan, uploaded through torch for a ho
 import numpy as np
 
 from .ray_objects import _columns
-from .transmission import _FanFrame, _absorption_profile, _boundary_spec, _lag_spec
+from ._fan_frame import (_FanFrame, _absorption_profile, _arrival_columns, _arrival_lags, _boundary_spec, _device_arrivals,
+                         _lag_spec)
 
 
 def _bilinear(x, y, x_grid, y_grid, values):
@@ -142,25 +143,6 @@ class Arrivals:
                 f"{len(self.range_indices)} ranges)")
 
 
-def _device_arrivals(f, cols):
-    """The arrivals of the frame `f` (a _FanFrame after to_device and absorb) at its receiver depths and the save columns
-    `cols`, left on the device -> (offsets int64 [R * n + 1], tube int32, w, T, p, I float64 [n_arrivals]): the count, the scan
-    and the emit entries, in ``Arrivals``' order."""
-    import torch
-    R, n = len(f.depths), len(cols)
-    counts = torch.empty(R * n, dtype=torch.int64, device=f.dev)
-    f.run("arrival_counts", f.d_depths.data_ptr(), R, cols, counts.data_ptr())
-    offsets = torch.zeros(R * n + 1, dtype=torch.int64, device=f.dev)
-    torch.cumsum(counts, 0, out=offsets[1:])
-    total = int(offsets[-1].item())
-    tube = torch.empty(total, dtype=torch.int32, device=f.dev)
-    w, T, P, I = (torch.empty(total, dtype=torch.float64, device=f.dev) for _ in range(4))
-    if total:
-        f.run("arrivals", f.d_depths.data_ptr(), R, cols, offsets.data_ptr(), total, tube.data_ptr(), w.data_ptr(),
-              T.data_ptr(), P.data_ptr(), I.data_ptr())
-    return offsets, tube, w, T, P, I
-
-
 def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=None, device=0, absorption=None,
              bottom_loss=None, surface_loss=None):
     """Ray-tube arrivals of ``rays`` (a ``RayFan`` from ``shoot_rays``) at ``receiver_depths`` (metres, positive down,
@@ -195,10 +177,7 @@ def arrivals(rays, receiver_depths, environment, flatearth=True, range_indices=N
     phase = None
     lag = _lag_spec(bottom_loss)
     if lag is not None:
-        import torch
-        from .signal import _arrival_lags
-        group = torch.repeat_interleave(torch.arange(R * n, device=f.dev), offsets[1:] - offsets[:-1])
-        col = torch.from_numpy(cols.astype(np.int64)).to(f.dev)[group % n]
+        col = _arrival_columns(f, offsets, cols)
         phase = _arrival_lags(f, lag, col, tube, w).cpu().numpy() if len(tube) else np.zeros(0)
     cin, rin, zin = f.tables
     xs = f.xf[cols]

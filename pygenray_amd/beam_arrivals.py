@@ -11,12 +11,9 @@ sum.  There is no CPU path.
 import numpy as np
 
 from . import _lib
-from .coherent import _needs_counts, _phase_index
+from ._fan_frame import (_arrival_columns, _arrival_lengths, _band, _band_absorption, _check_fits, _coherent_frame, _min_width,
+                         _one_zero, _per_column, _phase_index, _pulse, _synthesise, _to_host)
 from .ray_objects import _columns
-from .reflection import BottomReflection
-from .signal import _check_fits, _inv_sigma, _per_column, _to_host
-from .spectrum import _arrival_lengths, _band_absorption, _synthesise
-from .transmission import _FanFrame, _absorption_profile, _boundary_spec
 
 _ARRIVAL_BYTES = 28          # tube, image, phase_index int32 and time, amplitude float64
 
@@ -77,19 +74,10 @@ class BeamArrivals:
 def _beam_frame(rays, receiver_depths, env, min_width, range_indices, absorption, bottom_loss, surface_loss, flatearth, who):
     """Everything ``beam_pressure_field`` and ``arrivals`` refuse without a GPU -> (frame, cols, min_width, profile, boundary,
     counts); ``absorption`` None, a scalar or a pair (a callable is the caller's)."""
-    w = float(min_width)
-    if not (np.isfinite(w) and w > 0):
-        raise ValueError("min_width must be finite and > 0")
-    if isinstance(bottom_loss, BottomReflection):
-        raise ValueError("beam_pressure_field does not yet apply a complex bottom phase: a BottomReflection as bottom_loss is "
-                         "refused (its magnitude alone would be wrong physics); pass bottom_loss=reflection.loss for the "
-                         "loss without the phase")
-    profile = None if absorption is None else _absorption_profile(absorption)
-    boundary = _boundary_spec(rays, bottom_loss, surface_loss)
-    f = _FanFrame(rays, receiver_depths, env, flatearth, who)
-    counts = _needs_counts(rays)
-    cols = _columns(range_indices, len(f.x))
-    return f, cols, w, profile, boundary, counts
+    w = _min_width(min_width)
+    f, profile, boundary, counts = _coherent_frame(rays, receiver_depths, env, absorption, bottom_loss, surface_loss, flatearth,
+                                                   who, beams=True)
+    return f, _columns(range_indices, len(f.x)), w, profile, boundary, counts
 
 
 def _device_beam_arrivals(f, cols, min_width, curvature, profile, boundary, counts, extra_bytes=0, fixed_bytes=0):
@@ -125,8 +113,7 @@ def _sum_terms(T, amp, qa):
     arrivals one zero each (the entries refuse null pointers)"""
     import torch
     if len(T) == 0:
-        return (torch.zeros(1, dtype=torch.float64, device=T.device), torch.zeros(1, dtype=torch.float64, device=T.device),
-                torch.zeros(1, dtype=torch.int32, device=T.device))
+        return _one_zero(T.device), _one_zero(T.device), _one_zero(T.device, torch.int32)
     return T, amp * amp, qa
 
 
@@ -162,18 +149,7 @@ def beam_received_signal(rays, receiver_depths, env, frequency, bandwidth, t0, d
     as there.  ``bandwidth=0`` is the CW limit: every sample equals ``beam_pressure_field(...)[j, column]`` bit for bit.  The
     pulse arguments, their errors and the memory check are ``received_signal``'s; ``min_width``, ``curvature``, the weights
     and every other error are ``beam_arrivals``'.  A device-resident fan is processed where it is and stays device resident."""
-    f0 = float(frequency)
-    if not (np.isfinite(f0) and f0 >= 0):
-        raise ValueError("frequency must be finite and >= 0 Hz")
-    rs = _inv_sigma(bandwidth)
-    step = float(dt)
-    if not (np.isfinite(step) and step > 0):
-        raise ValueError("dt must be finite and > 0 seconds")
-    if isinstance(n_times, (bool, float)) or int(n_times) != n_times or int(n_times) < 1:
-        raise ValueError("n_times must be an integer >= 1")
-    nt = int(n_times)
-    if nt > 65535 * 256:
-        raise ValueError(f"n_times must be <= {65535 * 256}")
+    f0, rs, step, nt = _pulse(frequency, bandwidth, dt, n_times)
     f, cols, w, profile, boundary, counts = _beam_frame(rays, receiver_depths, env, min_width, range_indices, absorption,
                                                         bottom_loss, surface_loss, flatearth, "beam_received_signal")
     R, n = len(f.depths), len(cols)
@@ -203,15 +179,8 @@ def beam_transfer_function(rays, receiver_depths, env, frequencies, min_width=10
     ``transfer_function``'s; with a callable the arrival's path length L is the mean of its tube's two rays at the arrival's
     column.  ``min_width``, ``curvature``, the boundary weights and every other error are ``beam_arrivals``'.  A
     device-resident fan is processed where it is and stays device resident."""
-    freq = np.asarray(frequencies, dtype=float)
-    if freq.ndim != 1 or len(freq) == 0:
-        raise ValueError("frequencies must be a non-empty 1-D sequence")
-    freq = np.ascontiguousarray(freq)
-    if not np.all(np.isfinite(freq)) or np.any(freq < 0):
-        raise ValueError("frequencies must be finite and >= 0 Hz")
+    freq = _band(frequencies)
     F = len(freq)
-    if F > 65535 * 256:
-        raise ValueError(f"at most {65535 * 256} frequencies per call")
     alpha = _band_absorption(absorption, freq) if callable(absorption) else None
     f, cols, w, profile, boundary, counts = _beam_frame(rays, receiver_depths, env, min_width, range_indices,
                                                         None if callable(absorption) else absorption, bottom_loss,
@@ -228,12 +197,10 @@ def beam_transfer_function(rays, receiver_depths, env, frequencies, min_width=10
                                                          fixed_bytes=0 if alpha is None else 8 * len(f.x) * len(f.rays))
     La = None
     if alpha is not None:
-        La = torch.zeros(1, dtype=torch.float64, device=f.dev)
+        La = _one_zero(f.dev)
         if len(tube):
             # the mean of the tube's two rays at the arrival's column: L_k + 0.5 (L_k+1 - L_k)
-            group = torch.repeat_interleave(torch.arange(R * n, device=f.dev), offsets[1:] - offsets[:-1])
-            col = torch.from_numpy(cols.astype(np.int64)).to(f.dev)[group % n]
-            La = _arrival_lengths(f, col, tube, 0.5).contiguous()
+            La = _arrival_lengths(f, _arrival_columns(f, offsets, cols), tube, 0.5).contiguous()
     T, I, qa = _sum_terms(T, amp, qa)
     tred = f.upload(np.tile(reduce, R))
     re, im = (torch.empty((R, n, F), dtype=torch.float64, device=f.dev) for _ in range(2))

@@ -9,7 +9,7 @@ CPU path.  ``transmission_loss``, ``beam_transmission_loss`` and ``arrivals`` ta
 import numpy as np
 
 from .ray_objects import _columns
-from .transmission import _TracedFan, _check_flatearth, _loss_table, _save_grid
+from ._fan_frame import _TracedFan, _check_flatearth, _loss_table, _save_grid
 
 
 def boundary_loss(rays, environment, bottom_loss=None, surface_loss=None, range_indices=None, flatearth=True, device=0):

@@ -8,54 +8,14 @@ fan, uploaded through torch for a host fan.  There is no CPU path.
 """
 import numpy as np
 
-from . import _lib
-from .reflection import BottomReflection
-from .transmission import (_FanFrame, _TracedFan, _absorption_profile, _boundary_spec, _check_flatearth, _lag_spec,
-                           _loss_table, _ptr, _save_grid)
+from ._fan_frame import (_TracedFan, _check_flatearth, _coherent_frame, _frequency, _kappa, _lag_spec, _loss_table, _min_width,
+                         _phase_index, _needs_counts, _save_grid)
 
 
-def _needs_counts(rays):
-    """False for a fan none of whose rays bounced; True for a bounced fan whose bounce log holds every bounce; a bounced fan
-    without such a log is refused.  Nothing is fetched or launched."""
-    total = np.asarray(rays.n_botts, dtype=np.int64) + np.asarray(rays.n_surfs, dtype=np.int64)
-    if len(total) == 0 or not total.any():
-        return False
-    if not rays._has_bounce_log():
-        raise ValueError("the fan's rays bounce and it has no bounce log: the caustic index needs the bounces at every save "
-                         "range, trace the fan with shoot_rays(..., max_bounces=K)")
-    log = rays.__dict__.get("_bounces")
-    K = log.capacity if log is not None else rays.__dict__["_dev"].K
-    if int(total.max()) > K:
-        raise ValueError(f"the fan's bounce log overflowed: a ray bounces {int(total.max())} times and the log holds {K} "
-                         f"(max_bounces={int(total.max())} holds every bounce)")
-    return True
-
-
-def _kappa(f, nb, ns):
-    """kappa [S][M] int32 on the device of the traced fan `f` (a _TracedFan after to_device) from the per-sample bounce counts
-    nb, ns [S][M] int32 on that device (None, None: a fan without bounces)"""
-    import torch
-    S, M = len(f.x), len(f.rays)
-    kappa = torch.empty((S, M), dtype=torch.int32, device=f.dev)
-    if f.handle is not None:
-        f.handle.caustic_index(_ptr(nb), _ptr(ns), kappa.data_ptr(), f.stream)
-    else:
-        _lib.caustic_index_device(f.env.device, f._host_fan("zs"), M, S, _ptr(nb), _ptr(ns), kappa.data_ptr(), f.stream)
-    return kappa
-
-
-def _phase_index(f, counts):
-    """q [S][M] int32 on the device of the frame `f` (a _FanFrame after to_device and absorb(..., counts=counts)): the tubes'
-    phase index in quarter cycles, kappa + 2 n_surf where the tube's two rays have bounced alike and -1 (the tube adds
-    nothing) elsewhere; kappa itself for a fan without bounces (`counts` False)."""
-    import torch
-    nb, ns = f.d_counts if counts else (None, None)
-    q = _kappa(f, nb, ns)
-    if counts:
-        # on the device: kappa + 2 n_surf where the tube's two rays have bounced alike, -1 (the tube adds nothing) elsewhere
-        same = (nb[:, :-1] == nb[:, 1:]) & (ns[:, :-1] == ns[:, 1:])
-        q[:, :-1] = torch.where(same, q[:, :-1] + 2 * ns[:, :-1], torch.full_like(q[:, :-1], -1))
-    return q
+def _loss_db(p):
+    """a complex pressure -> -20 log10 |p| dB (+inf where it is 0)"""
+    with np.errstate(divide="ignore"):
+        return -20.0 * np.log10(np.abs(p))
 
 
 def caustic_index(rays, env=None, flatearth=True, device=0):
@@ -73,8 +33,6 @@ def caustic_index(rays, env=None, flatearth=True, device=0):
     if len(rays) < 2:
         raise ValueError("caustic_index needs a fan of at least 2 rays (one ray tube)")
     counts = _needs_counts(rays)
-    import torch
-    handle = rays.__dict__.get("_dev")
     if env is not None:
         _check_flatearth(env, flatearth)
         f = _TracedFan(rays, _save_grid(rays), env, flatearth).to_device(device)
@@ -86,17 +44,10 @@ def caustic_index(rays, env=None, flatearth=True, device=0):
     elif counts:
         raise ValueError("caustic_index of a fan with bounces needs `env`, the environment the fan was traced in")
     else:
-        M = len(rays)
-        dev = torch.device("cuda", handle._env.device if handle is not None else int(device))
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        if handle is not None:
-            kappa = torch.empty((handle.S, M), dtype=torch.int32, device=dev)
-            handle.caustic_index(0, 0, kappa.data_ptr(), stream)
-        else:
-            z = torch.from_numpy(np.ascontiguousarray(np.asarray(rays.zs, dtype=float).T)).to(dev)
-            kappa = torch.empty(tuple(z.shape), dtype=torch.int32, device=dev)
-            _lib.caustic_index_device(dev.index, z.data_ptr(), M, z.shape[0], 0, 0, kappa.data_ptr(), stream)
-            torch.cuda.current_stream(dev).synchronize()               # (the upload is freed when this returns)
+        handle = rays.__dict__.get("_dev")
+        S = handle.S if handle is not None else np.shape(rays.zs)[1]        # (no frame: of the save ranges only their number)
+        f = _TracedFan(rays, np.empty(S), None, flatearth).on_device(handle._env.device if handle is not None else int(device))
+        kappa = _kappa(f, None, None)
     return kappa[:, :-1].cpu().numpy().T.astype(np.int64)
 
 
@@ -123,13 +74,9 @@ def pressure_field(rays, receiver_depths, env, frequency, absorption=None, botto
     take their square root through I).  The frame and the sound speed are ``transmission_loss``'s.  A fan with bounces
     needs its bounce log (``shoot_rays(..., max_bounces=K)``): ``ValueError`` otherwise.  A device-resident fan is
     processed where it is and stays device resident."""
-    f0 = float(frequency)
-    if not (np.isfinite(f0) and f0 >= 0):
-        raise ValueError("frequency must be finite and >= 0 Hz")
-    profile = None if absorption is None else _absorption_profile(absorption)
-    boundary = _boundary_spec(rays, bottom_loss, surface_loss)
-    f = _FanFrame(rays, receiver_depths, env, flatearth, "pressure_field")
-    counts = _needs_counts(rays)
+    f0 = _frequency(frequency)
+    f, profile, boundary, counts = _coherent_frame(rays, receiver_depths, env, absorption, bottom_loss, surface_loss, flatearth,
+                                                   "pressure_field")
     f.to_device(device).absorb(profile, boundary, counts=counts)      # (one run of the boundary loss: weights and counts)
     import torch
     q = _phase_index(f, counts)
@@ -148,10 +95,8 @@ def coherent_transmission_loss(rays, receiver_depths, env, frequency, absorption
                                flatearth=True, device=0):
     """Coherent ray-tube transmission loss: ``-20 log10 |p|`` dB re 1 m of ``pressure_field``, whose arguments it takes
     (``+inf`` where no ray tube reaches or the paths cancel, NaN in the source's own column)."""
-    p = pressure_field(rays, receiver_depths, env, frequency, absorption=absorption, bottom_loss=bottom_loss,
-                       surface_loss=surface_loss, flatearth=flatearth, device=device)
-    with np.errstate(divide="ignore"):
-        return -20.0 * np.log10(np.abs(p))
+    return _loss_db(pressure_field(rays, receiver_depths, env, frequency, absorption=absorption, bottom_loss=bottom_loss,
+                                   surface_loss=surface_loss, flatearth=flatearth, device=device))
 
 
 def beam_pressure_field(rays, receiver_depths, env, frequency, min_width=10.0, curvature=True, absorption=None,
@@ -183,19 +128,10 @@ def beam_pressure_field(rays, receiver_depths, env, frequency, min_width=10.0, c
     speed and the bathymetry are ``beam_transmission_loss``'s.  A fan with bounces needs its bounce log
     (``shoot_rays(..., max_bounces=K)``): ``ValueError`` otherwise.  A device-resident fan is processed where it is and stays
     device resident."""
-    f0, w = float(frequency), float(min_width)
-    if not (np.isfinite(f0) and f0 >= 0):
-        raise ValueError("frequency must be finite and >= 0 Hz")
-    if not (np.isfinite(w) and w > 0):
-        raise ValueError("min_width must be finite and > 0")
-    if isinstance(bottom_loss, BottomReflection):
-        raise ValueError("beam_pressure_field does not yet apply a complex bottom phase: a BottomReflection as bottom_loss is "
-                         "refused (its magnitude alone would be wrong physics); pass bottom_loss=reflection.loss for the "
-                         "loss without the phase")
-    profile = None if absorption is None else _absorption_profile(absorption)
-    boundary = _boundary_spec(rays, bottom_loss, surface_loss)
-    f = _FanFrame(rays, receiver_depths, env, flatearth, "beam_pressure_field")
-    counts = _needs_counts(rays)
+    f0, w = float(frequency), float(min_width)          # (both converted before either is refused)
+    f0, w = _frequency(f0), _min_width(w)
+    f, profile, boundary, counts = _coherent_frame(rays, receiver_depths, env, absorption, bottom_loss, surface_loss, flatearth,
+                                                   "beam_pressure_field", beams=True)
     f.to_device(device).absorb(profile, boundary, counts=counts)      # (one run of the boundary loss: weights and counts)
     import torch
     q = _phase_index(f, counts)
@@ -209,11 +145,9 @@ def coherent_beam_transmission_loss(rays, receiver_depths, env, frequency, min_w
                                     bottom_loss=None, surface_loss=None, flatearth=True, device=0):
     """Coherent Gaussian-beam transmission loss: ``-20 log10 |p|`` dB re 1 m of ``beam_pressure_field``, whose arguments it
     takes (``+inf`` where no beam reaches or the paths cancel, NaN in the source's own column)."""
-    p = beam_pressure_field(rays, receiver_depths, env, frequency, min_width=min_width, curvature=curvature,
-                            absorption=absorption, bottom_loss=bottom_loss, surface_loss=surface_loss, flatearth=flatearth,
-                            device=device)
-    with np.errstate(divide="ignore"):
-        return -20.0 * np.log10(np.abs(p))
+    return _loss_db(beam_pressure_field(rays, receiver_depths, env, frequency, min_width=min_width, curvature=curvature,
+                                        absorption=absorption, bottom_loss=bottom_loss, surface_loss=surface_loss,
+                                        flatearth=flatearth, device=device))
 
 
 __all__ = ["caustic_index", "pressure_field", "coherent_transmission_loss", "beam_pressure_field",

@@ -12,7 +12,7 @@ import numpy as np
 from . import _lib
 from .environment import _unpack_envi
 from .ray_objects import EigenRays, RayFan
-from .transmission import _TracedFan, _check_flatearth, _save_grid
+from ._fan_frame import _TracedFan, _check_flatearth, _save_grid
 
 
 def _grid(v, name, most):

@@ -10,33 +10,9 @@ There is no CPU path.  The FFTs of ``received_waveform`` are NumPy's, on the hos
 import numpy as np
 
 from . import _lib
-from .coherent import _needs_counts
+from ._fan_frame import (_arrival_lengths, _arrival_terms, _band, _band_absorption, _check_fits, _coherent_frame, _lag_spec,
+                         _one_zero, _per_column, _synthesise, _to_host, _fft_sizes)   # noqa: F401  (_fft_sizes lived here)
 from .ray_objects import _columns
-from .signal import _arrival_terms, _check_fits, _per_column, _to_host
-from .transmission import _FanFrame, _absorption_profile, _boundary_spec, _lag_spec
-
-
-def _band_absorption(absorption, freq):
-    """``absorption(freq)``, a callable's dB/km at every frequency, checked -> alpha in dB per METRE (F,); the callable's own
-    errors propagate"""
-    a = np.asarray(absorption(freq.copy()), dtype=float)
-    if a.shape != freq.shape:
-        raise ValueError(f"absorption(frequencies) must give one value in dB/km per frequency: shape {freq.shape}, not "
-                         f"{a.shape}")
-    if not np.all(np.isfinite(a)) or np.any(a < 0):
-        raise ValueError("absorption(frequencies) must be finite and >= 0 dB/km")
-    return np.ascontiguousarray(a / 1000.0)
-
-
-def _arrival_lengths(f, col, tube, w):
-    """L_a of every arrival, on the device: the path length of the tube's two edge rays at the arrival's column, interpolated
-    by the arrival's w in three separate operations, L_k + w (L_k+1 - L_k)"""
-    L = f.path_integral(None, np.ones(1))                             # (S, M): the path length, alpha = 1
-    k = tube.long()
-    L0, L1 = L[col, k], L[col, k + 1]
-    d = L1 - L0
-    d = w * d
-    return L0 + d
 
 
 def transfer_function(rays, receiver_depths, env, frequencies, range_indices=None, absorption=None, bottom_loss=None,
@@ -66,23 +42,11 @@ def transfer_function(rays, receiver_depths, env, frequencies, range_indices=Non
     with bounces needs its bounce log, ``shoot_rays(..., max_bounces=K)``).  ``ValueError`` when ``R * n * F`` complex entries
     do not fit in the free device memory, before any kernel runs.  A device-resident fan is processed where it is and stays
     device resident."""
-    freq = np.asarray(frequencies, dtype=float)
-    if freq.ndim != 1 or len(freq) == 0:
-        raise ValueError("frequencies must be a non-empty 1-D sequence")
-    freq = np.ascontiguousarray(freq)
-    if not np.all(np.isfinite(freq)) or np.any(freq < 0):
-        raise ValueError("frequencies must be finite and >= 0 Hz")
+    freq = _band(frequencies)
     F = len(freq)
-    if F > 65535 * 256:
-        raise ValueError(f"at most {65535 * 256} frequencies per call")
-    alpha = profile = None
-    if callable(absorption):
-        alpha = _band_absorption(absorption, freq)
-    elif absorption is not None:
-        profile = _absorption_profile(absorption)
-    boundary = _boundary_spec(rays, bottom_loss, surface_loss)
-    f = _FanFrame(rays, receiver_depths, env, flatearth, "transfer_function")
-    counts = _needs_counts(rays)
+    alpha = _band_absorption(absorption, freq) if callable(absorption) else None
+    f, profile, boundary, counts = _coherent_frame(rays, receiver_depths, env, None if callable(absorption) else absorption,
+                                                   bottom_loss, surface_loss, flatearth, "transfer_function")
     cols = _columns(range_indices, len(f.x))
     R, n = len(f.depths), len(cols)
     reduce = _per_column(0.0 if t_reduce is None else t_reduce, n, "t_reduce", "reduction time")
@@ -93,7 +57,7 @@ def transfer_function(rays, receiver_depths, env, frequencies, range_indices=Non
     offsets, tube, w, T, I, qa, col, *phi = _arrival_terms(f, cols, profile, boundary, counts, lag)
     La = None
     if alpha is not None:
-        La = _arrival_lengths(f, col, tube, w) if len(tube) else torch.zeros(1, dtype=torch.float64, device=f.dev)
+        La = _arrival_lengths(f, col, tube, w) if len(tube) else _one_zero(f.dev)
     tred = f.upload(np.tile(reduce, R))
     re, im = (torch.empty((R, n, F), dtype=torch.float64, device=f.dev) for _ in range(2))
     if lag is None:
@@ -105,55 +69,6 @@ def transfer_function(rays, receiver_depths, env, frequencies, range_indices=Non
                                  phi[0].data_ptr(), 0 if La is None else La.data_ptr(), tred.data_ptr(), freq, alpha,
                                  re.data_ptr(), im.data_ptr(), f.stream)
     return _to_host(f, cols, re, im)
-
-
-def _fft_sizes(n_source, n_times, n_fft):
-    """(n_times, n_fft) of ``received_waveform`` from what was given, checked"""
-    def whole(v, name):
-        if isinstance(v, (bool, float)) or int(v) != v or int(v) < 1:
-            raise ValueError(f"{name} must be an integer >= 1")
-        return int(v)
-    if n_times is None and n_fft is None:
-        raise ValueError("give n_times, n_fft or both")
-    nt = None if n_times is None else whole(n_times, "n_times")
-    if n_fft is None:
-        nf = 1 << (nt + n_source - 1).bit_length()
-    else:
-        nf = whole(n_fft, "n_fft")
-    nt = nf if nt is None else nt
-    if nf < n_source:
-        raise ValueError(f"n_fft ({nf}) must be at least the length of source ({n_source})")
-    if nt > nf:
-        raise ValueError(f"n_times ({nt}) must be <= n_fft ({nf})")
-    return nt, nf
-
-
-def _synthesise(H_of, source, dt, carrier, t0, n_times, n_fft):
-    """``received_waveform``'s checks and its FFT synthesis around a transfer function: ``H_of(frequencies, t_reduce)`` -> H
-    (R, n, n_fft), as ``transfer_function`` gives it -> u (R, n, n_times).  Shared with ``beam_received_waveform``."""
-    s = np.asarray(source)
-    if s.ndim != 1 or len(s) == 0:
-        raise ValueError("source must be a non-empty 1-D sequence of complex baseband samples")
-    s = s.astype(np.complex128)
-    if not np.all(np.isfinite(s)):
-        raise ValueError("source must be finite")
-    step, fc = float(dt), float(carrier)
-    if not (np.isfinite(step) and step > 0):
-        raise ValueError("dt must be finite and > 0 seconds")
-    if not (np.isfinite(fc) and fc >= 1.0 / (2.0 * step)):
-        raise ValueError("carrier must be finite and at least 1 / (2 dt) Hz: the band carrier +- 1 / (2 dt) must not reach "
-                         "negative frequencies")
-    nt, nf = _fft_sizes(len(s), n_times, n_fft)
-    start = np.asarray(t0, dtype=float)
-    if not np.all(np.isfinite(start)):
-        raise ValueError("t0 must be finite")
-    nu = np.fft.fftfreq(nf, step)
-    Shat = nf * np.fft.ifft(s, nf)
-    H = H_of(fc + nu, start)
-    cyc = fc * np.broadcast_to(start, (H.shape[1],))
-    turn = np.exp(2j * np.pi * (cyc - np.rint(cyc)))
-    u = np.fft.fft(Shat * H, axis=-1) / nf * turn[None, :, None]
-    return np.ascontiguousarray(u[:, :, :nt])
 
 
 def received_waveform(rays, receiver_depths, env, source, dt, carrier, t0, n_times=None, n_fft=None, range_indices=None,

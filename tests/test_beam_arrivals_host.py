@@ -5,6 +5,7 @@ strip the tubes leave empty, and the exports, signatures, prototypes and refusal
 here is the one beam_arrivals_reference.py and DESIGN.md record; its bound is twice it."""
 import ctypes
 import inspect
+import os
 
 import numpy as np
 import pytest
@@ -208,18 +209,18 @@ def test_the_new_functions_are_exported_with_their_siblings_arguments():
 
 def test_the_four_entries_are_bound_from_a_header_of_their_own():
     from pygenray_amd import _lib
-    assert len(_lib.BEAM_ARRIVALS_PROTOTYPES) == 4
+    own = _lib.HEADER_PROTOTYPES["pgr_beam_arrivals.h"]
+    assert len(own) == 4
     V, D, I32, I64 = ctypes.c_void_p, ctypes.c_double, ctypes.c_int32, ctypes.c_int64
     fan_head, buf_head = [V, V, V, V], [V, V, V, V, I64, I32, V, V, V, V]
     counts, emit = [V, V, I64, D, V, I32, V, V], [V, V, I64, D, V, I32, I32, V, I64, V, V, V, V, V, V]
-    assert _lib.BEAM_ARRIVALS_PROTOTYPES == {
+    assert own == {
         "pgr_fan_beam_arrival_counts_w": (ctypes.c_int, fan_head + counts),
         "pgr_fan_beam_arrivals_w": (ctypes.c_int, fan_head + emit),
         "pgr_beam_arrival_counts_device_w": (ctypes.c_int, buf_head + counts),
         "pgr_beam_arrivals_device_w": (ctypes.c_int, buf_head + emit)}
-    for name in _lib.BEAM_ARRIVALS_PROTOTYPES:
-        for other in (_lib.PROTOTYPES, _lib.COHERENT_PROTOTYPES, _lib.SIGNAL_PROTOTYPES, _lib.SPECTRUM_PROTOTYPES,
-                      _lib.REFLECTION_PROTOTYPES, _lib.BEAM_COHERENT_PROTOTYPES):
+    for name in own:
+        for other in [protos for h, protos in _lib.HEADER_PROTOTYPES.items() if h != "pgr_beam_arrivals.h"]:
             assert name not in other
     for name in ("beam_arrival_counts", "beam_arrivals"):
         assert callable(getattr(_lib, name + "_device")) and callable(getattr(_lib.FanHandle, name))
@@ -228,10 +229,15 @@ def test_the_four_entries_are_bound_from_a_header_of_their_own():
     assert text.count(inc) == 1 and text.index('#include "pgr_beam_coherent.h"') < text.index(inc) < text.rindex("#ifdef __cplusplus")
     hip = open(_lib.CSRC + "/pgr_hip.hip").read()
     assert hip.index('#include "pgr_beam_phase.h"') < hip.index('#include "pgr_beam_arrivals.h"')
-    assert "BEAM_ARRIVALS_HEADER" in inspect.getsource(_lib.build) and "pgr_beam_arrivals.h" in inspect.getsource(_lib.load)
-    assert "BEAM_ARRIVALS_PROTOTYPES" in inspect.getsource(_lib.load)
-    from pygenray_amd.transmission import _FanFrame
-    assert '"beam_arrival_counts", "beam_arrivals"' in inspect.getsource(_FanFrame.run)
+    # the header is one of those the binding reads and the build depends on, and load() binds every name of it
+    header = [h for h in _lib.HEADERS if os.path.basename(h) == "pgr_beam_arrivals.h"]
+    assert len(header) == 1 and os.path.samefile(os.path.dirname(header[0]), os.path.dirname(_lib.HEADER))
+    assert header[0] in _lib.build_dependencies()
+    assert all(_lib.PROTOTYPES[name] == proto for name, proto in own.items())
+    # a host fan's ts go to both entries, with its zs and ps
+    from pygenray_amd._fan_frame import _entry_takes
+    for name in ("beam_arrival_counts", "beam_arrivals"):
+        assert _entry_takes(name) == (("ts", "zs", "ps"), True)
 
 
 def _all_four(fan, env, depths=(100.0,), **kw):

@@ -4,6 +4,7 @@ oracle's fan -- the caustic bound, the definition's identities, and the exports,
 The values measured here are the ones beam_pressure_reference.py and DESIGN.md record; every bound is twice its value."""
 import ctypes
 import inspect
+import os
 
 import numpy as np
 import pytest
@@ -244,14 +245,14 @@ def test_the_new_functions_are_exported():
 def test_the_two_entries_are_bound_from_a_header_of_their_own():
     from pygenray_amd import _lib
     names = {"pgr_fan_beam_pressure_w": 13, "pgr_beam_pressure_device_w": 19}
-    assert set(_lib.BEAM_COHERENT_PROTOTYPES) == set(names)
+    own = _lib.HEADER_PROTOTYPES["pgr_beam_coherent.h"]
+    assert set(own) == set(names)
     V, D, I32, I64 = ctypes.c_void_p, ctypes.c_double, ctypes.c_int32, ctypes.c_int64
-    assert _lib.BEAM_COHERENT_PROTOTYPES["pgr_fan_beam_pressure_w"] == (ctypes.c_int, [V, V, V, V, D, V, V, I64, D, I32, V, V, V])
-    assert _lib.BEAM_COHERENT_PROTOTYPES["pgr_beam_pressure_device_w"] == (
+    assert own["pgr_fan_beam_pressure_w"] == (ctypes.c_int, [V, V, V, V, D, V, V, I64, D, I32, V, V, V])
+    assert own["pgr_beam_pressure_device_w"] == (
         ctypes.c_int, [V, V, V, V, I64, I32, V, V, V, V, D, V, V, I64, D, I32, V, V, V])
     for name in names:
-        for other in (_lib.PROTOTYPES, _lib.COHERENT_PROTOTYPES, _lib.SIGNAL_PROTOTYPES, _lib.SPECTRUM_PROTOTYPES,
-                      _lib.REFLECTION_PROTOTYPES):
+        for other in [protos for h, protos in _lib.HEADER_PROTOTYPES.items() if h != "pgr_beam_coherent.h"]:
             assert name not in other
     assert callable(_lib.beam_pressure_device) and callable(_lib.FanHandle.beam_pressure)
     text = open(_lib.HEADER).read()
@@ -259,7 +260,11 @@ def test_the_two_entries_are_bound_from_a_header_of_their_own():
     assert text.count(inc) == 1 and text.index('#include "pgr_reflection.h"') < text.index(inc) < text.rindex("#ifdef __cplusplus")
     hip = open(_lib.CSRC + "/pgr_hip.hip").read()
     assert hip.index('#include "pgr_phase.h"') < hip.index('#include "pgr_beam_phase.h"')
-    assert "pgr_beam_coherent.h" in inspect.getsource(_lib.load)
+    # the header is one of those the binding reads and the build depends on, and load() binds every name of it
+    header = [h for h in _lib.HEADERS if os.path.basename(h) == "pgr_beam_coherent.h"]
+    assert len(header) == 1 and os.path.samefile(os.path.dirname(header[0]), os.path.dirname(_lib.HEADER))
+    assert header[0] in _lib.build_dependencies()
+    assert all(_lib.PROTOTYPES[name] == proto for name, proto in own.items())
 
 
 def _both(fan, env, *a, **kw):

@@ -457,7 +457,7 @@ def test_products_with_boundary_loss_bit_identical_to_the_restatements(pr, which
     assert _same(pr.boundary_loss(fan, env, FAN_BOTTOM, FAN_SURFACE, range_indices=[-1, 3], flatearth=flatearth), B_ref[:, [80, 3]])
     # the counts the post-pass forms on the device, through the keep list of the fan handle (rays were dropped) and from
     # the uploaded log of the host fan: RayFan.bounce_counts, which NumPy forms from the fetched log
-    from pygenray_amd.transmission import _TracedFan, _boundary_spec, _save_grid
+    from pygenray_amd._fan_frame import _TracedFan, _boundary_spec, _save_grid
     for f in (fan, eager):
         dB, dnb, dns = _TracedFan(f, _save_grid(f), env, flatearth).to_device(0).boundary_loss(
             _boundary_spec(f, FAN_BOTTOM, FAN_SURFACE), counts=True)

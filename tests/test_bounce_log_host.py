@@ -9,7 +9,7 @@ import pytest
 import bounce_reference as bref
 import pygenray_amd as pr
 from pygenray_amd.ray_objects import BounceLog, RayFan
-from pygenray_amd.transmission import _loss_table
+from pygenray_amd._fan_frame import _loss_table
 
 
 def _random_events(rng, x, n):

@@ -269,7 +269,8 @@ def test_the_new_functions_are_exported():
     assert inspect.signature(pr.caustic_index).parameters["env"].default is None
     assert isinstance(inspect.getattr_static(pr.Arrivals, "caustics"), property)
     from pygenray_amd import _lib
+    own = _lib.HEADER_PROTOTYPES["pgr_coherent.h"]
     for name in ("pgr_fan_caustic_index", "pgr_caustic_index_device", "pgr_fan_pressure_w", "pgr_pressure_device_w"):
-        assert name in _lib.COHERENT_PROTOTYPES and name not in _lib.PROTOTYPES
-    assert len(_lib.COHERENT_PROTOTYPES) == 4
-    assert len(_lib.COHERENT_PROTOTYPES["pgr_pressure_device_w"][1]) == 16 and len(_lib.COHERENT_PROTOTYPES["pgr_fan_pressure_w"][1]) == 10
+        assert name in own and all(name not in protos for h, protos in _lib.HEADER_PROTOTYPES.items() if h != "pgr_coherent.h")
+    assert len(own) == 4
+    assert len(own["pgr_pressure_device_w"][1]) == 16 and len(own["pgr_fan_pressure_w"][1]) == 10

@@ -267,15 +267,15 @@ def test_library_exports_every_declared_symbol():
     """Every prototype include/pgr.h declares (as the binding parses them) resolves in the built library, and the three
     longest parameter lists are bound with the arity counted by hand from the header."""
     from pygenray_amd import _lib
-    declared = set(_lib.PROTOTYPES)
+    declared = set(_lib.HEADER_PROTOTYPES["pgr.h"])
     assert {"pgr_env_create", "pgr_shoot_fan", "pgr_shoot_fan_device", "pgr_last_error"} <= declared
     assert len(declared) == 50
     path = _lib.build()  # hipcc cross-compiles gfx950 without a GPU
     L = ctypes.CDLL(path)
-    for sym in sorted(declared):
+    for sym in sorted(_lib.PROTOTYPES):          # (pgr.h's own and those of the headers it includes)
         assert hasattr(L, sym), sym
     for name, arity in (("pgr_shoot_fan_device", 21), ("pgr_arrivals_device_w", 21), ("pgr_boundary_loss_device", 22)):
-        assert len(_lib.PROTOTYPES[name][1]) == arity, name
+        assert len(_lib.HEADER_PROTOTYPES["pgr.h"][name][1]) == arity, name
     # the code object is gfx950 only
     out = subprocess.run(["/opt/rocm/lib/llvm/bin/llvm-readelf", "--notes", path], capture_output=True, text=True)
     if out.returncode == 0 and "amdgcn" in out.stdout:
@@ -366,6 +366,39 @@ def test_library_older_than_the_header_is_refused(tmp_path):
     assert "REFUSED" in out.stdout, out.stderr
     assert re.search(r"does not export pgr_\w+", out.stdout) and "older than the header" in out.stdout
     assert "import __graft_entry__ as g; g.build()" in out.stdout
+    # ... and naming the header that declares the symbol: include/pgr.h here, an included header for a library that has all
+    # of pgr.h's own symbols and none of the later ones
+    from pygenray_amd import _lib
+    missing = re.search(r"does not export (pgr_\w+), which include/(pgr\w*\.h) declares", out.stdout)
+    assert missing and missing.group(2) == "pgr.h" and missing.group(1) in _lib.HEADER_PROTOTYPES["pgr.h"]
+    src.write_text("".join("void %s(void) {}\n" % name for name in _lib.HEADER_PROTOTYPES["pgr.h"]))
+    subprocess.run([os.environ.get("CC", "cc"), "-shared", "-fPIC", "-o", str(stub), str(src)], check=True)
+    out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True)
+    assert "REFUSED" in out.stdout and "older than the header" in out.stdout, out.stderr
+    missing = re.search(r"does not export (pgr_\w+), which include/(pgr\w*\.h) declares", out.stdout)
+    second = os.path.basename(_lib.HEADERS[1])
+    assert missing and missing.group(2) == second != "pgr.h" and missing.group(1) in _lib.HEADER_PROTOTYPES[second]
+    assert not re.search(r"pgr_\w+\.h", out.stdout.replace(second, ""))             # (no list of every header)
+
+
+def test_a_name_declared_in_two_headers_is_refused(tmp_path):
+    """_lib.read_abi: the main header and the `#include "pgr_*.h"` lines of it, in order; a name the main header (or an earlier
+    include) declares and an included header declares again is a PgrError naming both files."""
+    from pygenray_amd import _lib
+    main = tmp_path / "pgr.h"
+    main.write_text('#define PGR_ONE 1\nint pgr_a(int n);\n/* #include "pgr_not.h" */\n#include <stdint.h>\n'
+                    '#include "pgr_x.h"\n#include "pgr_y.h"\n')
+    (tmp_path / "pgr_x.h").write_text("int pgr_b(double v);\n")
+    (tmp_path / "pgr_y.h").write_text("void pgr_c(void);\n")
+    paths, by_header, constants = _lib.read_abi(str(main))
+    assert [os.path.basename(h) for h in paths] == ["pgr.h", "pgr_x.h", "pgr_y.h"] and constants == {"PGR_ONE": 1}
+    assert {h: list(protos) for h, protos in by_header.items()} == {"pgr.h": ["pgr_a"], "pgr_x.h": ["pgr_b"], "pgr_y.h": ["pgr_c"]}
+    (tmp_path / "pgr_y.h").write_text("void pgr_c(void);\nint pgr_a(int n);\n")
+    with pytest.raises(_lib.PgrError, match=r"pgr_a is declared in pgr\.h and again in pgr_y\.h"):
+        _lib.read_abi(str(main))
+    (tmp_path / "pgr_y.h").unlink()
+    with pytest.raises(_lib.PgrError, match=r"pgr_y\.h: the C ABI header cannot be read"):
+        _lib.read_abi(str(main))
 
 
 def test_no_cpu_fallback_and_oracle_not_imported_by_product(tmp_path):

@@ -4,12 +4,13 @@ tests/reflection_reference.py, every refusal of ``BottomReflection`` / ``fluid_h
 without one, and the waveguide over a fluid half-space on the CPU oracle's fan against the ray-theoretic image sum.  The values
 measured here are the ones reflection_reference.py records; the GPU test (tests/test_reflection.py) uses twice them as bounds."""
 import inspect
+import os
 
 import numpy as np
 import pytest
 
 import pygenray_amd as pr
-from pygenray_amd.transmission import _boundary_spec, _lag_spec, _loss_table
+from pygenray_amd._fan_frame import _boundary_spec, _lag_spec, _loss_table
 
 import bounce_reference as bref
 import coherent_reference as cref
@@ -209,18 +210,19 @@ def test_the_names_are_exported_and_no_public_signature_changed():
 def test_the_four_entries_are_bound_from_a_header_of_their_own():
     from pygenray_amd import _lib
     names = {"pgr_fan_pressure_phi": 11, "pgr_pressure_device_phi": 17, "pgr_signal_device_phi": 15, "pgr_spectrum_device_phi": 15}
-    assert set(_lib.REFLECTION_PROTOTYPES) == set(names)
+    own = _lib.HEADER_PROTOTYPES["pgr_reflection.h"]
+    assert set(own) == set(names)
     for name, arity in names.items():
-        assert len(_lib.REFLECTION_PROTOTYPES[name][1]) == arity, name
-        for other in (_lib.PROTOTYPES, _lib.COHERENT_PROTOTYPES, _lib.SIGNAL_PROTOTYPES, _lib.SPECTRUM_PROTOTYPES):
+        assert len(own[name][1]) == arity, name
+        for other in [protos for h, protos in _lib.HEADER_PROTOTYPES.items() if h != "pgr_reflection.h"]:
             assert name not in other
     # each is its sibling's prototype with one more pointer directly after q
     import ctypes
-    for new, (old, table, at) in {"pgr_fan_pressure_phi": ("pgr_fan_pressure_w", _lib.COHERENT_PROTOTYPES, 4),
-                                  "pgr_pressure_device_phi": ("pgr_pressure_device_w", _lib.COHERENT_PROTOTYPES, 10),
-                                  "pgr_signal_device_phi": ("pgr_signal_device", _lib.SIGNAL_PROTOTYPES, 6),
-                                  "pgr_spectrum_device_phi": ("pgr_spectrum_device", _lib.SPECTRUM_PROTOTYPES, 6)}.items():
-        ret, args = _lib.REFLECTION_PROTOTYPES[new]
+    for new, (old, table, at) in {"pgr_fan_pressure_phi": ("pgr_fan_pressure_w", _lib.HEADER_PROTOTYPES["pgr_coherent.h"], 4),
+                                  "pgr_pressure_device_phi": ("pgr_pressure_device_w", _lib.HEADER_PROTOTYPES["pgr_coherent.h"], 10),
+                                  "pgr_signal_device_phi": ("pgr_signal_device", _lib.HEADER_PROTOTYPES["pgr_signal.h"], 6),
+                                  "pgr_spectrum_device_phi": ("pgr_spectrum_device", _lib.HEADER_PROTOTYPES["pgr_spectrum.h"], 6)}.items():
+        ret, args = own[new]
         oret, oargs = table[old]
         assert ret is oret and args[:at] == oargs[:at] and args[at] is ctypes.c_void_p and args[at + 1:] == oargs[at:], new
         assert oargs[at - 1] is ctypes.c_void_p                          # (q)
@@ -232,7 +234,11 @@ def test_the_four_entries_are_bound_from_a_header_of_their_own():
     assert text.count(inc) == 1 and text.index('#include "pgr_spectrum.h"') < text.index(inc) < text.rindex("#ifdef __cplusplus")
     hip = open(_lib.CSRC + "/pgr_hip.hip").read()
     assert hip.index('#include "pgr_signal.h"') < hip.index('#include "pgr_reflect.h"') < hip.index('#include "pgr_spectrum.h"')
-    assert "REFLECTION_HEADER" in inspect.getsource(_lib.build) and "REFLECTION_PROTOTYPES" in inspect.getsource(_lib.load)
+    # the header is one of those the binding reads and the build depends on, and load() binds every name of it
+    header = [h for h in _lib.HEADERS if os.path.basename(h) == "pgr_reflection.h"]
+    assert len(header) == 1 and os.path.samefile(os.path.dirname(header[0]), os.path.dirname(_lib.HEADER))
+    assert header[0] in _lib.build_dependencies()
+    assert all(_lib.PROTOTYPES[name] == proto for name, proto in own.items())
 
 
 # ---- the restated sums --------------------------------------------------------------------------------------------------------

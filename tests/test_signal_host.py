@@ -118,9 +118,9 @@ def test_pulse_sigma():
         assert s == pytest.approx(math.sqrt(math.log(2)) / (math.pi * B), rel=1e-15) and s == sref.pulse_sigma(B)
         # the half-power points of the spectrum exp(-2 pi^2 sigma^2 nu^2) of the envelope lie B apart: |Ehat(B/2)|^2 = 1/2
         assert math.exp(-2 * math.pi ** 2 * s ** 2 * (B / 2) ** 2) ** 2 == pytest.approx(0.5, rel=1e-14)
-        from pygenray_amd.signal import _inv_sigma
+        from pygenray_amd._fan_frame import _inv_sigma
         assert _inv_sigma(B) == sref.inv_sigma(B) == pytest.approx(1.0 / s, rel=1e-15)
-    from pygenray_amd.signal import _inv_sigma
+    from pygenray_amd._fan_frame import _inv_sigma
     assert _inv_sigma(0) == 0.0
     for bad in (-1.0, math.nan, math.inf):
         with pytest.raises(ValueError, match="bandwidth must be finite and >= 0"):
@@ -214,8 +214,9 @@ def test_the_new_names_are_exported_and_the_entry_is_bound_from_its_own_header()
     assert sig["flatearth"].default is True and sig["device"].default == 0
     assert "centre frequency" in pr.received_signal.__doc__ and "not varied across the band" in pr.received_signal.__doc__
     from pygenray_amd import _lib
-    assert len(_lib.SIGNAL_PROTOTYPES) == 1 and len(_lib.SIGNAL_PROTOTYPES["pgr_signal_device"][1]) == 14
-    assert "pgr_signal_device" not in _lib.PROTOTYPES and "pgr_signal_device" not in _lib.COHERENT_PROTOTYPES
+    own = _lib.HEADER_PROTOTYPES["pgr_signal.h"]
+    assert len(own) == 1 and len(own["pgr_signal_device"][1]) == 14
+    assert all("pgr_signal_device" not in protos for h, protos in _lib.HEADER_PROTOTYPES.items() if h != "pgr_signal.h")
     assert callable(_lib.signal_device)
     # pgr.h hands the entry to a C caller through the header of its own
     text = open(_lib.HEADER).read()

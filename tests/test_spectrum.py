@@ -298,10 +298,10 @@ def test_band_absorption_against_pressure_field_at_each_frequency_within_the_edg
         assert (bound[lit] < 0.01 * per_group(amp0 * np.sqrt(Wmin))[lit]).all()
     print(f"band absorption: worst ratio to the bound {worst:.3e}")
     # L_a itself: the restatement's three operations on path_length and Arrivals.w, bit for bit
-    from pygenray_amd.signal import _arrival_terms
-    from pygenray_amd.spectrum import _arrival_lengths
-    from pygenray_amd.transmission import _FanFrame
-    from pygenray_amd.coherent import _needs_counts
+    from pygenray_amd._fan_frame import _arrival_terms
+    from pygenray_amd._fan_frame import _arrival_lengths
+    from pygenray_amd._fan_frame import _FanFrame
+    from pygenray_amd._fan_frame import _needs_counts
     from pygenray_amd.ray_objects import _columns
     fr = _FanFrame(fan, d, env, False, "test").to_device(0)
     _, tube, w, _, _, _, col = _arrival_terms(fr, _columns(cols, len(fr.x)), None, None, _needs_counts(fan))

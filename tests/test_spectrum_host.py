@@ -4,6 +4,7 @@ that ties received_waveform's three lines to the time-domain sum of a Gaussian p
 10^(-alpha L / 20), and the interface and the argument errors refused before anything reaches the device."""
 import inspect
 import math
+import os
 from decimal import Decimal, getcontext
 
 import numpy as np
@@ -224,8 +225,9 @@ def test_the_new_names_are_exported_and_the_entry_is_bound_from_its_own_header()
     doc = " ".join(pr.received_waveform.__doc__.split())
     assert "CIRCULAR with the period ``n_fft * dt``" in doc and "wraps around" in doc
     from pygenray_amd import _lib
-    assert len(_lib.SPECTRUM_PROTOTYPES) == 1 and len(_lib.SPECTRUM_PROTOTYPES["pgr_spectrum_device"][1]) == 14
-    for other in (_lib.PROTOTYPES, _lib.COHERENT_PROTOTYPES, _lib.SIGNAL_PROTOTYPES):
+    own = _lib.HEADER_PROTOTYPES["pgr_spectrum.h"]
+    assert len(own) == 1 and len(own["pgr_spectrum_device"][1]) == 14
+    for other in [protos for h, protos in _lib.HEADER_PROTOTYPES.items() if h != "pgr_spectrum.h"]:
         assert "pgr_spectrum_device" not in other
     assert callable(_lib.spectrum_device)
     # pgr.h hands the entry to a C caller through the header of its own
@@ -235,7 +237,11 @@ def test_the_new_names_are_exported_and_the_entry_is_bound_from_its_own_header()
     # the kernel's header is the last of the translation unit, and the build depends on the ABI header
     hip = open(_lib.CSRC + "/pgr_hip.hip").read()
     assert hip.rstrip().splitlines()[-1].startswith('#include "pgr_spectrum.h"')
-    assert "SPECTRUM_HEADER" in inspect.getsource(_lib.build)
+    # the header is one of those the binding reads and the build depends on, and load() binds every name of it
+    header = [h for h in _lib.HEADERS if os.path.basename(h) == "pgr_spectrum.h"]
+    assert len(header) == 1 and os.path.samefile(os.path.dirname(header[0]), os.path.dirname(_lib.HEADER))
+    assert header[0] in _lib.build_dependencies()
+    assert all(_lib.PROTOTYPES[name] == proto for name, proto in own.items())
 
 
 # ---- argument errors, no GPU --------------------------------------------------------------------------------------------------
@@ -347,6 +353,6 @@ def test_received_waveform_refuses_bad_arguments_before_the_device():
 
 
 def test_fft_sizes_default_as_documented():
-    from pygenray_amd.spectrum import _fft_sizes
+    from pygenray_amd._fan_frame import _fft_sizes
     assert _fft_sizes(73, 751, None) == (751, 1024) and _fft_sizes(24, 1000, None) == (1000, 1024)
     assert _fft_sizes(25, 1000, None) == (1000, 2048) and _fft_sizes(3, None, 64) == (64, 64) and _fft_sizes(3, 5, 7) == (5, 7)
