@@ -2,7 +2,9 @@
 the bounce post-pass with its per-sample counts (pgr_bounce.h), the caustic scan and the coherent tube sum (pgr_phase.h), the
 pulse and band sums (pgr_signal.h, pgr_spectrum.h), the three sums with a bottom lag (pgr_reflect.h) and the coherent beam sum
 with and without its curvature term (pgr_beam_phase.h: beam_pressure_device, FanHandle.beam_pressure, beam_pressure_field,
-coherent_beam_transmission_loss; min_width MIN_WIDTHS[seed % 3]) -- on that sweep's
+coherent_beam_transmission_loss; min_width MIN_WIDTHS[seed % 3]) and the terms of that sum listed as arrivals, with the pulse
+and band sums over the list (pgr_beam_arrivals.h: beam_arrival_counts_device, beam_arrivals_device, the two FanHandle entries,
+beam_arrivals, beam_received_signal, beam_transfer_function) -- on that sweep's
 environments: tables starting at -400 km, mirrored (negative, reversed) frames, non-uniform range grids, stretched and
 power-of-two depth grids, the bathymetry on a grid of its own, flat-earth mapped tables.  Bit for bit, NaN patterns and integers
 included, in the reference arithmetic only.  The cases, receivers and columns are test_products_random_env.py's own objects.
@@ -18,11 +20,22 @@ Level 1 (one test per case): random_case's fan shot as a FanHandle with a bounce
 host-pointer shot, every 8th bouncing ray's log against the oracle's step trace -- then the buffer entries on the surviving
 rays' rows and the fetched log against the NumPy restatements on the same raw tables, the _phi entries at a lag of zero against
 their siblings, and the handle's own entries (rows or sample-blocked, dropped rays through the keep list) against the buffer
-entries.  The beam sums are written between sentinels, and once with neither weights nor q.
+entries.  The beam sums are written between sentinels, and once with neither weights nor q.  The beam arrivals: four lists by
+count, exclusive scan and emit (BEAM_LISTS: W and q with and without the curvature term, neither weights nor q, Wb and q), the
+counts and the five arrays between sentinels, against beam_arrivals_reference.beam_arrivals, which is written from the
+definition with every tube at once; the weighted lists summed by spectrum_device at the one frequency f, I = amp * amp formed
+with torch, against beam_pressure_device's own field and the tube-by-tube restatement's on the requested columns (two
+independent references and two kernels tied together); signal_device over the curvature-1 list against signal_sum over the
+restated list; spectrum_device over the Wb list with Thorp's alpha and L0 + 0.5 (L1 - L0) of the device's path lengths
+against spectrum_sum over the restated list with the restated mean lengths; then all of it through the handle, equal.
 Level 2 (API_CASES x forwards / backwards x flatearth off / on): pr.shoot_rays with a log, device resident and not,
 against the un-logged fan, then every public product on both fans against the restatements fed by tests/frame_independent.py
 alone: frame, launch slowness and bottom slope there share no code with the package.  The beams take the loss pair of the
-bottom (a BottomReflection is refused, once per frame).
+bottom (a BottomReflection is refused, once per frame).  beam_arrivals with and without the curvature term (every array, the
+echoed range_indices, ranges, intensity = amplitude ** 2, nothing in the source's column; the host fan is asked for the last
+column as -1), beam_transfer_function at [f] equal to the beam field on the requested columns, beam_received_signal and
+beam_transfer_function with t_reduce and Thorp's absorption against the restated sums over the restated lists.
+beam_arrivals_reference.fan_beam_arrivals, which takes its frame from the package, is not used here.
 
 The sign of p.  The restatements read p by the convention the kernels were written under, so a shared sign error would pass
 every comparison above.  beam_pressure_reference.eikonal_share holds it by the eikonal equation alone: at a fixed range
@@ -39,8 +52,19 @@ For the beam sum the rule adds, over the columns other than the source's: at lea
 those non-zero, an otherwise valid tube with q < 0, and the curvature term changing at least half of the non-zero cells; over
 the sweep, 30 of the 40 cases each with a kept surface image, a kept bottom image, and tubes both at the floor min_width and
 above it (39 each on the oracle's fans).
+For the beam arrivals the rule adds (ARRIVAL_RULES, from the restated lists alone; no case is exempt, an infinite amplitude is
+an arrival like any other): at least 1000 arrivals, none at the source's column, at least half of the (receiver, column) groups
+away from the source lit, no amplitude whose square is subnormal and no NaN time, the curvature term changing at least half of
+the times, a requested column whose pulse window (+- 8 sigma) holds a beam arrival and a pulse sum that is not zero everywhere,
+and the restated weighted lists summed at f equal to the tube-by-tube restatement's BP / BP_linear bit for bit (which a wrong
+sign of p_m in a copy of the list's restatement breaks on every case tried: every time changes and nothing else); over the
+sweep, 30 of the 40 cases each with a surface-image and a bottom-image arrival, and every emitted q 0 ... 3 seen.  On the
+oracle's fans: 1122 (seed 228) ... 43 879 (seed 226) arrivals at level 1, lit groups 0.78 (seed 213) ... 1, 39 cases each with
+a surface image (not 228) and a bottom image (not 204), 1934 and 1668 infinite amplitudes on seeds 202 and 225; the 48 frames
+1402 ... 35 113 arrivals, lit groups 0.625 (seed 213 backwards) ... 1, both columns away from the source with a pulse in every
+frame, 1529 ... 2432 infinite amplitudes in seed 202's four frames.
 Passed over: none -- not one of the 40 cases or of the 12 API seeds (all four frames of each) missed a condition of the first
-paragraph.  Exempt from the beam conditions alone, and still compared bit for bit: seed 225 at level 1 -- it saves two columns
+paragraph or of the beam arrivals'.  Exempt from the beam conditions alone, and still compared bit for bit: seed 225 at level 1 -- it saves two columns
 and its path integral is -9.9e6 dB on 39 rays of the lit one, so their weights 10^(-(A + B) / 10) overflow; 56 live tubes hold
 such a ray, three of them 2.0 - 2.9 km wide and within 4 sigma of all 64 receivers, and inf - inf makes every cell NaN (the
 tube sum, a top hat, stays finite at 5 receivers) -- and seed 202 at level 2, whose weights overflow in the same way: 6 - 12 %
@@ -50,6 +74,7 @@ inf / finite a NaN (which also has the composition and the 
 import numpy as np
 import pytest
 
+import beam_arrivals_reference as ba
 import beam_pressure_reference as bpr
 import bounce_reference as bref
 import coherent_reference as cref
@@ -86,6 +111,7 @@ HAND_MADE = ([2.0, 11.0, 35.0, 80.0], [0.9, 0.55, 0.35, 0.5], [-150.0, -20.0, -7
 MAX_ROWS = 400000                                         # step attempts of the oracle's trace of the longest rays
 MARK = -7.25
 PAD = 130                                                 # entries either side of a beam output that must stay as they were
+BEAM_KEYS = ("tube", "image", "time", "amplitude", "q")   # a beam-arrival list's arrays, in the order the emit entries take them
 
 
 def bottom_of(pr, seed):  # noqa: F811
@@ -154,6 +180,11 @@ def _restate(fan, frame, beta, bottom, seed, depths, cols, w_min):
         sel = [0] + [c for c in cols if c != 0]
         bare = _complex(*bpr.beam_pressure(zs[:, sel], ps[:, sel], ts[:, sel], xf[sel], *tab, floor[sel], w_min, None, None, f))
         r["BP_bare"] = bare[:, [sel.index(c) for c in cols]]
+        # the beam arrivals from the definition, every tube at once: with and without the curvature term, with neither weights
+        # nor q, and without volume absorption in the weights
+        for name, w_, q_, curvature in BEAM_LISTS:
+            r[name] = ba.beam_arrivals(zs, ps, ts, xf, p0, depths, cin, rin, zin, floor, w_min,
+                                       {"W": W, "Wb": Wb, None: None}[w_], None if q_ is None else q, cols, curvature)
     arr = r["arr"] = pref.tube_arrivals(zs, ps, ts, xf, p0, depths, cols, cin, rin, zin, W)
     r["arr_b"] = pref.tube_arrivals(zs, ps, ts, xf, p0, depths, cols, cin, rin, zin, Wb)       # (no volume absorption)
     # per arrival: the phase index, the lag and the path length of its tube at its column
@@ -174,6 +205,20 @@ def _restate(fan, frame, beta, bottom, seed, depths, cols, w_min):
     r["freq"] = band_of(f)
     r["u_raw"] = rref.signal_sum(off, arr["T"], arr["I"], r["qa"], r["phi"], np.tile(r["t0"], R), f, r["rs"], dt,
                                  N_TIMES).reshape(R, n, N_TIMES)
+    if w_min is not None:
+        # the beam list summed: at the one frequency f without a reduction (the field itself), by the pulse, and -- the list
+        # without volume absorption, with the mean path length of each arrival's tube -- by the band (beam_band_sum)
+        a, a_b = r["ba"], r["ba_b"]
+        r["ba_field"] = spref.spectrum_sum(a["offsets"], a["time"], a["amplitude"] * a["amplitude"], a["q"], None,
+                                           np.zeros(R * n), [f], None).reshape(R, n)
+        lin = r["ba_linear"]
+        r["ba_field_linear"] = spref.spectrum_sum(lin["offsets"], lin["time"], lin["amplitude"] * lin["amplitude"], lin["q"], None,
+                                                  np.zeros(R * n), [f], None).reshape(R, n)
+        r["bu_raw"] = sref.signal_sum(a["offsets"], a["time"], a["amplitude"] * a["amplitude"], a["q"], np.tile(r["t0"], R), f,
+                                      r["rs"], dt, N_TIMES).reshape(R, n, N_TIMES)
+        kb = a_b["tube"].astype(np.int64)
+        colb = np.asarray(cols, dtype=np.int64)[np.repeat(np.arange(R * n), np.diff(a_b["offsets"])) % n]
+        r["bLa"] = spref.arrival_lengths(r["L"][kb, colb], r["L"][kb + 1, colb], 0.5)
     return r
 
 
@@ -182,6 +227,13 @@ def band_sum(r, alpha, R, n):
     a = r["arr_b"]
     return rref.spectrum_sum(a["offsets"], a["T"], a["I"], r["qa"], r["phi"], r["La"], np.tile(r["t0"], R), r["freq"],
                              alpha).reshape(R, n, N_FREQ)
+
+
+def beam_band_sum(r, alpha, R, n):
+    """the band sum of restate()'s beam arrivals without volume absorption in the weights, alpha (F,) dB/m per frequency"""
+    a = r["ba_b"]
+    return spref.spectrum_sum(a["offsets"], a["time"], a["amplitude"] * a["amplitude"], a["q"], r["bLa"], np.tile(r["t0"], R),
+                              r["freq"], alpha).reshape(R, n, N_FREQ)
 
 
 def at_source_nan(v, xf, cols):
@@ -209,6 +261,7 @@ def figures(r, xf, cols):
                 eikonal_share=r["eikonal"][0], eikonal_tubes=r["eikonal"][1])
     if "BP" in r:
         fig.update(beam_figures(r, xf))
+        fig.update(beam_arrival_figures(r, xf, cols))
     return fig
 
 
@@ -227,8 +280,43 @@ def beam_figures(r, xf):
                 sigma_both=bool((sigma[live] == r["w_min"]).any() and (sigma[live] > r["w_min"]).any()))
 
 
+def beam_arrival_figures(r, xf, cols):
+    """the beam arrivals' quantities of the seed rule, from the restated lists alone"""
+    a, lin, a_b = r["ba"], r["ba_linear"], r["ba_b"]
+    n = len(cols)
+    per = np.diff(a["offsets"]).reshape(-1, n)
+    at_source = np.asarray(xf)[np.asarray(cols)] == xf[0]
+    slot = np.repeat(np.arange(per.size), per.ravel()) % n
+    t_end = r["t0"] + (N_TIMES - 1) * r["dt"]
+    inside = (a["time"] >= r["t0"][slot] - 8.0 * r["sigma"]) & (a["time"] <= t_end[slot] + 8.0 * r["sigma"])
+    same_set = np.array_equal(a["offsets"], lin["offsets"]) and np.array_equal(a["tube"], lin["tube"])
+    with np.errstate(invalid="ignore"):
+        curved = float((a["time"] != lin["time"]).mean()) if same_set and len(a["time"]) else 0.0
+    away = ~at_source
+    # (the sums are 0.0 in the source's own column, which holds no arrivals; the field is NaN there)
+    field = all(_bits_equal(at_source_nan(r[k][:, :, None], xf, cols)[:, :, 0], r[ref][:, cols]) and (r[k][:, at_source] == 0).all()
+                for k, ref in (("ba_field", "BP"), ("ba_field_linear", "BP_linear")))
+    return dict(ba_arrivals=int(a["offsets"][-1]), ba_source_dark=bool((per[:, at_source] == 0).all()),
+                ba_lit_groups=float((per[:, away] > 0).mean()) if away.any() else 0.0,
+                ba_squares=bool(ba.no_subnormal_squares(a["amplitude"]) and ba.no_subnormal_squares(a_b["amplitude"])),
+                ba_times=bool(not np.isnan(a["time"]).any() and not np.isnan(a_b["time"]).any()), ba_curved=curved,
+                ba_columns_with_a_pulse=int(len(np.unique(slot[inside]))), ba_pulse_lit=bool((np.abs(r["bu_raw"]) > 0).any()),
+                ba_sums_to_field=bool(field), ba_infinite=int(np.isinf(a["amplitude"]).sum()),
+                ba_surface_image=bool((a["image"] == 1).any()), ba_bottom_image=bool((a["image"] == 2).any()),
+                ba_q=tuple(int(v) for v in np.unique(a["q"])))
+
+
+def _bits_equal(a, b):
+    return all((((x == y) | ((x != x) & (y != y))).all()) for x, y in ((a.real, b.real), (a.imag, b.imag)))
+
+
 BEAM_RULES = (("beam_finite", 0.5), ("beam_nonzero", 0.5), ("beam_left_out", 1), ("beam_curved", 0.5))
-BEAM_TALLIES = ("surface_image", "bottom_image", "sigma_both")
+BEAM_TALLIES = ("surface_image", "bottom_image", "sigma_both", "ba_surface_image", "ba_bottom_image")
+# the beam arrivals' conditions, which every case meets (none is exempt: an infinite amplitude is an arrival like any other)
+ARRIVAL_RULES = (("ba_arrivals", 1000), ("ba_source_dark", True), ("ba_lit_groups", 0.5), ("ba_squares", True), ("ba_times", True),
+                 ("ba_curved", 0.5), ("ba_columns_with_a_pulse", 1), ("ba_pulse_lit", True), ("ba_sums_to_field", True))
+# the lists of restate() and of level 1: (name, weights, q, curvature)
+BEAM_LISTS = (("ba", "W", "q", True), ("ba_linear", "W", "q", False), ("ba_bare", None, None, True), ("ba_b", "Wb", "q", True))
 BEAM_FLOOR = 30                                           # of the 40 level-1 cases, for each of BEAM_TALLIES
 
 
@@ -238,6 +326,8 @@ def misses(fig, beams=True):
              ("pulse_lit", True), ("eikonal_share", EIKONAL_SHARE))
     if beams and "beam_finite" in fig:
         rules += BEAM_RULES
+    if "ba_arrivals" in fig:
+        rules += ARRIVAL_RULES
     return [f"{k} {fig[k]} < {least}" for k, least in rules if not fig[k] >= least]
 
 
@@ -295,6 +385,7 @@ def cpu_check(level1=True, level2=True):
     out = []
     if level1:
         tally = dict(lag=0, surface=0, bottom=0, **{k: 0 for k in BEAM_TALLIES})
+        q_seen = set()
         for seed, flat in CASES:
             t = time.time()
             arrs, y0, kw, desc, mirrored = case_inputs(seed, flat)
@@ -307,11 +398,13 @@ def cpu_check(level1=True, level2=True):
             fig = figures(r, fan["x"], cols)
             for k in tally:
                 tally[k] += fig[k]
+            q_seen |= set(fig["ba_q"])
             missed = misses(fig, (seed, flat) not in BEAM_EXEMPT)
             out.append(((seed, flat), missed))
             print(f"seed {seed} flat {flat!s:5s} {time.time() - t:5.1f} s  misses {missed}  {fig}", flush=True)
-        print("level 1:", tally)
-        out.append(("level 1", [f"{k} {tally[k]} < {BEAM_FLOOR}" for k in BEAM_TALLIES if tally[k] < BEAM_FLOOR]))
+        print("level 1:", tally, "emitted q", sorted(q_seen))
+        out.append(("level 1", [f"{k} {tally[k]} < {BEAM_FLOOR}" for k in BEAM_TALLIES if tally[k] < BEAM_FLOOR]
+                    + [f"emitted q {sorted(q_seen)}"] * (q_seen != {0, 1, 2, 3})))
     if level2:
         for seed, lat in API_CASES:
             arrs, src, th, kw, desc = api_case(seed)
@@ -349,6 +442,14 @@ def _close(a, b, what, label):
     for x, y in ((a.real, b.real), (a.imag, b.imag)) if np.iscomplexobj(a) or np.iscomplexobj(b) else ((a, b),):
         bad = ~((x == y) | ((x != x) & (y != y)))
         assert not bad.any(), (label, what, int(bad.sum()), np.argwhere(bad)[:5].tolist(), x[bad][:5], y[bad][:5])
+
+
+def same_beam_arrivals(a, b, what, label):
+    """two beam-arrival lists (host dicts): the offsets and the integers equal and of one type, time and amplitude bit for bit"""
+    assert a["offsets"].dtype == b["offsets"].dtype and np.array_equal(a["offsets"], b["offsets"]), (label, what, "arrival counts")
+    for k in BEAM_KEYS:
+        assert a[k].dtype == b[k].dtype, (label, what, k, a[k].dtype, b[k].dtype)
+        _close(a[k], b[k], f"{what}: arrivals' {k}", label)
 
 
 class _Device:
@@ -396,6 +497,67 @@ class _Device:
         host = [a.cpu().numpy() for a in out]
         assert all((a[:PAD] == MARK).all() and (a[PAD + n:] == MARK).all() for a in host), "written outside the output"
         return _complex(*(a[PAD:PAD + n].reshape(self.R, S) for a in host))
+
+    def beam_list(self, cols, count, emit):
+        """the count, the scan and the emit of one beam-arrival walk, the counts and the five arrays written between sentinels
+        that are checked untouched before and behind -> device tensors (offsets, tube, image, time, amplitude, q)"""
+        torch = self.torch
+        G = self.R * len(cols)
+        counts = torch.full((PAD + G + PAD,), -7, dtype=torch.int64, device=self.dev)
+        count(counts[PAD:].data_ptr())
+        host = counts.cpu().numpy()
+        assert (host[:PAD] == -7).all() and (host[PAD + G:] == -7).all(), "written outside the counts"
+        assert (host[PAD:PAD + G] >= 0).all()
+        offsets = torch.zeros(G + 1, dtype=torch.int64, device=self.dev)
+        torch.cumsum(counts[PAD:PAD + G], 0, out=offsets[1:])
+        total = int(offsets[-1].item())
+        assert total > 0
+        out = {k: (self.f64 if k in ("time", "amplitude") else self.i32)(PAD + total + PAD) for k in BEAM_KEYS}
+        emit(offsets.data_ptr(), total, *(out[k][PAD:].data_ptr() for k in BEAM_KEYS))
+        for k, v in out.items():
+            host, mark = v.cpu().numpy(), MARK if k in ("time", "amplitude") else -7
+            assert (host[:PAD] == mark).all() and (host[PAD + total:] == mark).all(), f"written outside the arrivals' {k}"
+        return dict(offsets=offsets, **{k: v[PAD:PAD + total] for k, v in out.items()})
+
+    def beam_sums(self, lists, cols, L, t0, rs, dt, freq, alpha):
+        """the sums of pgr_spectrum.h and pgr_signal.h over the beam lists of one side, I = amp * amp formed as beam_arrivals.py
+        forms it: the weighted lists at the one frequency f without a reduction time or path lengths, the pulse of the
+        curvature-1 list, and the band of the list without volume absorption with the mean path length of each arrival's tube,
+        L [S][M] at (column, tube) and (column, tube + 1) as L0 + 0.5 (L1 - L0) in three operations -> complex host arrays"""
+        from pygenray_amd import _lib
+        torch = self.torch
+        n = len(cols)
+        G = self.R * n
+        zero, tstart = self.up(np.zeros(G)), self.up(np.tile(t0, self.R))
+        o = {}
+        for name, key in (("ba_field", "ba"), ("ba_field_linear", "ba_linear")):
+            a = lists[key]
+            I = a["amplitude"] * a["amplitude"]
+            re, im = self.f64(G, 1), self.f64(G, 1)
+            _lib.spectrum_device(self.env.device, a["offsets"].data_ptr(), G, a["time"].data_ptr(), I.data_ptr(), a["q"].data_ptr(),
+                                 0, zero.data_ptr(), [self.f], None, re.data_ptr(), im.data_ptr(), self.stream)
+            o[name] = _complex(re.cpu().numpy(), im.cpu().numpy()).reshape(self.R, n)
+        a = lists["ba"]
+        I = a["amplitude"] * a["amplitude"]
+        re, im = self.f64(G, N_TIMES), self.f64(G, N_TIMES)
+        _lib.signal_device(self.env.device, a["offsets"].data_ptr(), G, a["time"].data_ptr(), I.data_ptr(), a["q"].data_ptr(),
+                           tstart.data_ptr(), self.f, rs, dt, N_TIMES, re.data_ptr(), im.data_ptr(), self.stream)
+        o["bu_raw"] = _complex(re.cpu().numpy(), im.cpu().numpy()).reshape(self.R, n, N_TIMES)
+        a = lists["ba_b"]
+        I = a["amplitude"] * a["amplitude"]
+        group = torch.repeat_interleave(torch.arange(G, device=self.dev), a["offsets"][1:] - a["offsets"][:-1])
+        col = torch.from_numpy(np.asarray(cols, dtype=np.int64)).to(self.dev)[group % n]
+        k = a["tube"].long()
+        L0, L1 = L[col, k], L[col, k + 1]
+        step = L1 - L0
+        step = 0.5 * step
+        La = (L0 + step).contiguous()
+        o["bLa"] = La.cpu().numpy()
+        re, im = self.f64(G, N_FREQ), self.f64(G, N_FREQ)
+        _lib.spectrum_device(self.env.device, a["offsets"].data_ptr(), G, a["time"].data_ptr(), I.data_ptr(), a["q"].data_ptr(),
+                             La.data_ptr(), tstart.data_ptr(), freq, alpha, re.data_ptr(), im.data_ptr(), self.stream)
+        o["bH"] = _complex(re.cpu().numpy(), im.cpu().numpy()).reshape(self.R, n, N_FREQ)
+        return o
 
     def phase_index(self, kappa, nb, ns):
         """q [S][M] as coherent.py forms it on the device"""
@@ -535,7 +697,7 @@ def _level1(pr, seed, flat):  # noqa: F811
         h.caustic_index(o["B_nb"].data_ptr(), o["B_ns"].data_ptr(), o["kappa"].data_ptr(), d.stream)
         return o
 
-    def weights_and_sums(o, pressure, pressure_phi, counts, emit, beam):
+    def weights_and_sums(o, pressure, pressure_phi, counts, emit, beam, beam_counts, beam_emit):
         """what follows the per-ray arrays, through the tube entries given"""
         for name, src in (("W", o["A"] + o["B"]), ("Wb", o["B"])):
             o[name] = d.f64(S, M)
@@ -553,6 +715,13 @@ def _level1(pr, seed, flat):  # noqa: F811
         for name, W in (("arr", o["W"]), ("arr_b", o["Wb"])):
             o[name] = d.arrivals(cols, lambda c: counts(d.p0.data_ptr(), d.depths.data_ptr(), R, cols, c, d.stream),
                                  lambda *a: emit(d.p0.data_ptr(), d.depths.data_ptr(), R, cols, *a, d.stream, weights=W.data_ptr()))
+        # the beam arrivals: the four lists, then the sums over them
+        for name, w_, q_, curvature in BEAM_LISTS:
+            W_, q_ = 0 if w_ is None else o[w_].data_ptr(), 0 if q_ is None else o["q"].data_ptr()
+            head = (d.p0.data_ptr(), q_, floor.data_ptr(), d.depths.data_ptr(), R, w_min, cols)
+            o[name] = d.beam_list(cols, lambda c: beam_counts(*head, c, d.stream, weights=W_),
+                                  lambda *a: beam_emit(*head, int(curvature), *a, d.stream, weights=W_))
+        o.update(d.beam_sums(o, cols, o["L"], r["t0"], r["rs"], r["dt"], r["freq"], alpha_f))
         return o
 
     b = weights_and_sums(
@@ -561,7 +730,9 @@ def _level1(pr, seed, flat):  # noqa: F811
         lambda *a, **k: _lib.pressure_phi_device(env, *fanp, *dims, *a, **k),
         lambda *a: _lib.arrival_counts_device(env, fanp[1], fanp[2], *dims, *a),
         lambda *a, **k: _lib.arrivals_device(env, *fanp, *dims, *a, **k),
-        lambda *a, **k: _lib.beam_pressure_device(env, *fanp, *dims, *a, **k))
+        lambda *a, **k: _lib.beam_pressure_device(env, *fanp, *dims, *a, **k),
+        lambda *a, **k: _lib.beam_arrival_counts_device(env, *fanp, *dims, *a, **k),
+        lambda *a, **k: _lib.beam_arrivals_device(env, *fanp, *dims, *a, **k))
     for name in ("A", "L", "B", "Phi", "W", "Wb"):
         _close(b[name].cpu().numpy().T, r[name], name, label)
     for name in ("B", "Phi"):                                            # (the counts do not depend on the tables)
@@ -589,8 +760,22 @@ def _level1(pr, seed, flat):  # noqa: F811
     us, Hs = d.sums(b["arr"], b["arr_b"], qa, None, La, r["t0"], r["rs"], r["dt"], r["freq"], alpha_f)
     _close(u0, us, "signal_phi_device at a lag of zero", label)
     _close(H0, Hs, "spectrum_phi_device at a lag of zero", label)
+    # the beam arrivals: every list against the restatement from the definition; the weighted lists summed at f are the beam
+    # kernel's own field and the tube-by-tube restatement's on the requested columns (NaN in the source's own, where the list
+    # holds nothing and its sum is 0.0); the pulse and the band against the restated sums over the restated lists
+    for name, *_ in BEAM_LISTS:
+        same_beam_arrivals(_host(b[name]), r[name], f"beam_arrivals_device ({name})", label)
+    for name, of in (("ba_field", "BP"), ("ba_field_linear", "BP_linear")):
+        assert (b[name][:, xs[cols] == xs[0]] == 0).all(), (label, name, "at the source's column")
+        summed = at_source_nan(b[name][:, :, None], xs, cols)[:, :, 0]
+        _close(summed, b[of][:, cols], f"the beam list summed at f against beam_pressure_device's {of}", label)
+        _close(summed, r[of][:, cols], f"the beam list summed at f against the restated {of}", label)
+    _close(b["bu_raw"], r["bu_raw"], "signal_device over the beam list", label)
+    _close(b["bLa"], r["bLa"], "beam arrivals' mean path length", label)
+    _close(b["bH"], beam_band_sum(r, alpha_f, R, n), "spectrum_device over the beam list without volume absorption", label)
     # 5. the handle's own entries against the buffer entries
-    e = weights_and_sums(handle(), h.pressure, h.pressure_phi, h.arrival_counts, h.arrivals, h.beam_pressure)
+    e = weights_and_sums(handle(), h.pressure, h.pressure_phi, h.arrival_counts, h.arrivals, h.beam_pressure,
+                         h.beam_arrival_counts, h.beam_arrivals)
     for name in ("A", "L", "B", "Phi", "B_nb", "B_ns", "Phi_nb", "Phi_ns", "W", "Wb"):
         _close(e[name].cpu().numpy(), b[name].cpu().numpy(), f"the handle's {name}", label)
     assert np.array_equal(e["kappa"].cpu().numpy()[:, :-1], b["kappa"].cpu().numpy()[:, :-1]), (label, "the handle's caustic index")
@@ -598,6 +783,10 @@ def _level1(pr, seed, flat):  # noqa: F811
         _close(e[name], b[name], f"the handle's {name}", label)
     for name in ("arr", "arr_b"):
         same_arrivals(_host(e[name]), _host(b[name]), f"{label} (the handle's {name})")
+    for name, *_ in BEAM_LISTS:
+        same_beam_arrivals(_host(e[name]), _host(b[name]), f"the handle's beam arrivals ({name})", label)
+    for name in ("ba_field", "ba_field_linear", "bu_raw", "bLa", "bH"):
+        _close(e[name], b[name], f"the handle's {name}", label)
     h.close()
     nonuniform = float(np.ptp(np.diff(rin))) > 1e-6 * float(np.mean(np.diff(rin)))
     offset = abs(rin[-1] if mirrored else rin[0])
@@ -606,6 +795,7 @@ def _level1(pr, seed, flat):  # noqa: F811
                bottom=fig["bottom"], rays=M, traced=len(traced), arrivals=fig["arrivals"], K=K, kappa=fig["kappa_max_anywhere"],
                bounced_tubes=fig["bounced_tubes"], field_fill=fig["field_fill"], eikonal=fig["eikonal_share"],
                beam_nonzero=fig["beam_nonzero"], beam_finite=fig["beam_finite"], beam_left_out=fig["beam_left_out"],
+               ba_arrivals=fig["ba_arrivals"], ba_lit_groups=fig["ba_lit_groups"], ba_infinite=fig["ba_infinite"], ba_q=fig["ba_q"],
                **{k: fig[k] for k in BEAM_TALLIES})
     env.close()
     _RECORDS[(seed, flat)] = rec
@@ -633,6 +823,12 @@ def test_the_sweep_holds_what_it_is_meant_to(pr):  # noqa: F811
           f"{min(r['beam_finite'] for r in held):.3f} ... {max(r['beam_finite'] for r in held):.3f} outside BEAM_EXEMPT; valid tubes "
           f"with q < 0 "
           f"{min(r['beam_left_out'] for r in recs)} ... {max(r['beam_left_out'] for r in recs)}")
+    q_seen = sorted(set().union(*(rec["ba_q"] for rec in recs)))
+    print(f"beam arrivals {min(r['ba_arrivals'] for r in recs)} ... {max(r['ba_arrivals'] for r in recs)} per case, "
+          f"{sum(r['ba_arrivals'] for r in recs)} in all, {sum(r['ba_infinite'] for r in recs)} of infinite amplitude in "
+          f"{sum(r['ba_infinite'] > 0 for r in recs)} cases; lit groups away from the source "
+          f"{min(r['ba_lit_groups'] for r in recs):.3f} ... {max(r['ba_lit_groups'] for r in recs):.3f}; emitted q {q_seen}")
+    assert q_seen == [0, 1, 2, 3], q_seen
     for k, least in (("hbm", 6), ("lds", 6), ("blocked", 6), ("mirrored", 6), ("offset", 6), ("nonuniform", 6), ("flat", 6),
                      ("dropped", 4), ("lag", 30), ("surface", 30)) + tuple((k, BEAM_FLOOR) for k in BEAM_TALLIES):
         assert tally[k] >= least, (k, tally)
@@ -724,6 +920,9 @@ def _either_sign(pr, seed, flat):  # noqa: F811
             o[name] = _complex(re.cpu().numpy(), im.cpu().numpy())
         for name, curvature in (("BP", 1), ("BP_linear", 0)):
             o[name] = d.beam_pressure(h.beam_pressure, q, W, floor, w_min, curvature, S)
+        head = (d.p0.data_ptr(), q.data_ptr(), floor.data_ptr(), *tail, w_min, cols)
+        o["ba"] = d.beam_list(cols, lambda c: h.beam_arrival_counts(*head, c, d.stream, weights=W.data_ptr()),
+                              lambda *a: h.beam_arrivals(*head, 1, *a, d.stream, weights=W.data_ptr()))
         o["ttk"] = d.f64(M, *TTK_GRID)
         h.travel_time_kernel(grid_r.data_ptr(), TTK_GRID[0], grid_d.data_ptr(), TTK_GRID[1], S - 1, o["ttk"].data_ptr(), d.stream)
         o["front"] = dict(T=d.f64(n, M), z=d.f64(n, M), p=d.f64(n, M), turns=d.i32(n, M))
@@ -743,6 +942,7 @@ def _either_sign(pr, seed, flat):  # noqa: F811
         a, b = (v[name] if isinstance(v[name], np.ndarray) else v[name].cpu().numpy() for v in (po, ps))
         _close(a, b, f"{name} of the fan in the ODE sign", label)
     same_arrivals(_host(po["arr"]), _host(ps["arr"]), label + " (arrivals of the fan in the ODE sign)")
+    same_beam_arrivals(_host(po["ba"]), _host(ps["ba"]), "beam arrivals of the fan in the ODE sign", label)
     fs, fo = _host(ps["front"]), _host(po["front"])
     _close(fo["T"], fs["T"], "time_front T", label)
     assert np.array_equal(fo["turns"], fs["turns"]), (label, "time_front turns")
@@ -768,7 +968,9 @@ def test_fan_entries_agree_in_either_sign(pr, seed, flat):  # noqa: F811
     equal (z, p and the log's p with the sign bit flipped), and every product entry bit-equal given the same device arguments
     -- path_integral, boundary_loss (dB and lag tables, with nb / ns), caustic_index, intensity, beam_intensity,
     arrival_counts, arrivals (p in the stored sign from both), pressure, pressure_phi, beam_pressure with and without the
-    curvature term, travel_time_kernel on a grid of its own -- and time_front with z and p as the fan holds them.  The
+    curvature term, beam_arrival_counts and beam_arrivals (pgr_fan_beam_arrival_counts_w, pgr_fan_beam_arrivals_w: the list with
+    the curvature term, whose times read p for p_m and the curvature), travel_time_kernel on a grid of its own -- and
+    time_front with z and p as the fan holds them.  The
     stored-sign side is held to the restatements by test_kernels_and_fan_entries_on_random_raw_tables."""
     _either_sign(pr, seed, flat)
 
@@ -831,6 +1033,7 @@ def test_api_products_against_frames_derived_by_hand(pr, seed, lat, backwards, f
     f, absorption = r["f"], r["absorption"]
     u_ref = at_source_nan(r["u_raw"], xf, cols)
     H_ref = at_source_nan(band_sum(r, pr.thorp_absorption(r["freq"]) / 1000.0, R, n), xf, cols)
+    bH_ref = at_source_nan(beam_band_sum(r, pr.thorp_absorption(r["freq"]) / 1000.0, R, n), xf, cols)
     weights = dict(absorption=absorption, bottom_loss=bottom, surface_loss=SURFACE_DB)
     loss = dict(bottom_loss=bottom, surface_loss=SURFACE_DB)
     every = np.arange(S)
@@ -866,9 +1069,31 @@ def test_api_products_against_frames_derived_by_hand(pr, seed, lat, backwards, f
         with np.errstate(divide="ignore", invalid="ignore"):
             tl = -20.0 * np.log10(np.abs(field))
         _close(pr.coherent_beam_transmission_loss(fan_, depths, env, f, **beam), tl, "coherent_beam_transmission_loss", lab)
+        # the beam arrivals, with and without the curvature term, against the restatement from the definition; the host fan is
+        # asked for the last column as -1
+        asked = cols if fan_ is dev else [-1 if c == S - 1 else c for c in cols]
+        at_source = x[cols] == x[0]
+        for name, kw in (("ba", beam), ("ba_linear", dict(beam, curvature=False))):
+            a = pr.beam_arrivals(fan_, depths, env, range_indices=asked, **kw)
+            same_beam_arrivals(dict(offsets=a.offsets, tube=a.tube, image=a.image, time=a.time, amplitude=a.amplitude,
+                                    q=a.phase_index), r[name], f"beam_arrivals ({name})", lab)
+            assert np.array_equal(a.range_indices, cols) and _same(a.ranges, x[cols]) and _same(a.receiver_depths, depths), lab
+            assert _same(a.intensity, a.amplitude ** 2) and len(a) == len(r[name]["tube"]) > 0, lab
+            assert at_source.sum() == 1 and (np.diff(a.offsets).reshape(R, n)[:, at_source] == 0).all(), (lab, "the source's column")
+        # the list summed by the public sums: at f it is the field, in the pulse and the band the restated sums
+        H1 = pr.beam_transfer_function(fan_, depths, env, [f], range_indices=cols, **beam)
+        assert H1.shape == (R, n, 1) and np.isnan(H1[:, at_source].real).all() and np.isnan(H1[:, at_source].imag).all(), lab
+        _close(H1[:, :, 0], field[:, cols], "beam_transfer_function at f against beam_pressure_field", lab)
+        ub = pr.beam_received_signal(fan_, depths, env, f, r["band"], r["t0"], r["dt"], N_TIMES, range_indices=cols, **beam)
+        _close(ub, at_source_nan(r["bu_raw"], xf, cols), "beam_received_signal", lab)
+        Hb = pr.beam_transfer_function(fan_, depths, env, r["freq"], range_indices=cols, t_reduce=r["t0"], min_width=w_min,
+                                       flatearth=fe, absorption=pr.thorp_absorption, bottom_loss=bottom.loss, surface_loss=SURFACE_DB)
+        _close(Hb, bH_ref, "beam_transfer_function with Thorp's absorption", lab)
         if fan_ is dev:
             with pytest.raises(ValueError, match="does not yet apply a complex bottom phase"):
                 pr.beam_pressure_field(fan_, depths, env, f, **dict(beam, bottom_loss=bottom))
+            with pytest.raises(ValueError, match="does not yet apply a complex bottom phase"):
+                pr.beam_arrivals(fan_, depths, env, range_indices=cols, **dict(beam, bottom_loss=bottom))
             _in_place(dev)
         assert fan_.device_resident == (fan_ is dev), lab               # processed where it is
     _in_place(dev)
