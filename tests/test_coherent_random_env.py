@@ -971,7 +971,9 @@ def test_fan_entries_agree_in_either_sign(pr, seed, flat):  # noqa: F811
     curvature term, beam_arrival_counts and beam_arrivals (pgr_fan_beam_arrival_counts_w, pgr_fan_beam_arrivals_w: the list with
     the curvature term, whose times read p for p_m and the curvature), travel_time_kernel on a grid of its own -- and
     time_front with z and p as the fan holds them.  The
-    stored-sign side is held to the restatements by test_kernels_and_fan_entries_on_random_raw_tables."""
+    stored-sign side is held to the restatements by test_kernels_and_fan_entries_on_random_raw_tables; its travel_time_kernel
+    and time_front, which that test does not call, by tests/test_ttk_random_env.py (the kernel against ttk_reference and
+    ttk_independent on a grid of that module's, both fan entries against the buffer entries and front_reference)."""
     _either_sign(pr, seed, flat)
 
 
