@@ -74,6 +74,47 @@ PGR_CR_FN double pgr_mask_select(int m, double a, double b)
     return va.d;
 }
 
+// ---- decisions of a step attempt's tail (pgr_fan_kernel.h) that do not go through the condition register ----
+// all ones where a < b, zero elsewhere, for EVERY double a -- NaN, +-inf, zeros of both signs, subnormals -- given a finite
+// constant b != 0 and a finite `above` > b.  fmin drops a NaN (NaN < b is false: `above` - b > 0 says so) and caps +inf; the
+// difference of two doubles is zero only where they are equal (gradual underflow) and then +0 (b is not a zero, so the
+// (-0) - (+0) of pgr_sign_mask cannot occur); everywhere else it has the sign of a - b, overflow to -inf included.
+PGR_CR_FN int pgr_mask_lt_const(double a, double b, double above)
+{
+    return pgr_sign_mask(__builtin_fmin(a, above) - b);
+}
+// all ones where d >= 0, for d = t - t_bound of a committed step: t <= t_bound (the attempt clamps t_new), neither is NaN
+// (a NaN step is never accepted), so d <= 0 and "d >= 0" is "d is a zero".  Equal operands give +0; the one -0,
+// (-0) - (+0), would need t = -0, which a sum t + h with h > 0 never is and the clamp only copies from t_bound.
+PGR_CR_FN int pgr_mask_reached(double d)
+{
+    return ~pgr_sign_mask(d);
+}
+// RK45's step factor, SCIPY/rk.py:148-165, from pw = SAFETY * err ** -0.2 (NaN where the power is not a number):
+//   accepted:  min(MAX_FACTOR, pw), and min(1, that) behind a rejected attempt  ==  fmin(pw, limit), limit = 1 or MAX_FACTOR
+//   rejected:  max(MIN_FACTOR, pw)                                              ==  fmax(pw, MIN_FACTOR)
+// fmin / fmax return the other operand for a NaN: MAX_FACTOR (1 behind a rejection) and MIN_FACTOR, what the compare forms
+// `pw < MAX_FACTOR ? pw : MAX_FACTOR` and `pw > MIN_FACTOR ? pw : MIN_FACTOR` give.  The limit depends on the attempt
+// BEFORE this one only: it is formed ahead of the stages, off the chain error norm -> power -> factor -> h_abs.
+PGR_CR_FN double pgr_factor_limit(int m_prev_rejected, double max_factor)
+{
+    return pgr_mask_select(m_prev_rejected, 1.0, max_factor);
+}
+PGR_CR_FN double pgr_step_factor(int m_accepted, double pw, double limit, double min_factor)
+{
+    return pgr_mask_select(m_accepted, __builtin_fmin(pw, limit), __builtin_fmax(pw, min_factor));
+}
+// a lane's wait bits -- PGR_WAIT_PARKED: its step fired an event and waits for the service, PGR_WAIT_INIT: it (re)starts --
+// where the lane is still running, zero elsewhere: RUNNING (-1) is the only negative status, so the sign word of the status
+// is the mask.  One integer in a vector register per lane instead of three lane masks in scalar pairs: the gate's "anybody
+// parked" is one compare of this word with zero.
+#define PGR_WAIT_PARKED 1
+#define PGR_WAIT_INIT 2
+PGR_CR_FN int pgr_lane_pending(int status, int wait)
+{
+    return wait & (status >> 31);
+}
+
 // ---- generated by scripts/gen/gen_crmath_tables.py (mpmath, 400 bits) ----
 // sin(j/32), cos(j/32), j = 0..28, as double-double {hi, lo}
 PGR_CR_TABLE(double, pgr_cr_sincos_tab, 29 * 4) = {

@@ -686,7 +686,11 @@ struct Ctx {
         if (__builtin_expect(!x_guard, 0)) above = (z < e.b_zmin) & (x >= e.b_xlo) & (x <= e.b_xhi);
         const bool near_bottom = (pc > 0) & (pc <= 1.0) & !above;
         const bool near_vertical = (fabs(pc) > k_vert) & (fabs(pc) <= 1.0);
-        if (near_bottom | near_vertical) {
+        // "nobody near a boundary" is the common answer, and as the skip of a per-lane block it was a taken branch on
+        // every such trip (~80 cycles for a lone wave).  ONE wave-uniform test instead, the block out of line: a lane
+        // can be near only if NOT (|pc| <= k_vert) or NOT (z < zmin_eff) -- two plain compares, each its own ballot
+        // (a NaN answers "maybe", as it must); the exact per-lane tests decide inside.
+        if (__builtin_expect((ballot64(!(fabs(pc) <= k_vert)) | ballot64(!(z < zmin_eff))) != 0, 0)) {
             if (near_bottom) {
                 if (z > bathy(x)) g |= 2u;
             }

@@ -154,7 +154,10 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
     unsigned g = 0;
     int status = valid ? RUNNING : PGR_RAY_OK;
     if (valid && (q_flags & PGR_SKIP_NAN_Y0) && (y2 != y2)) status = PGR_RAY_SKIPPED;  // a parked eigenray bracket
-    bool need_init = true, rejected = false, parked = false;
+    // the lane's wait bits (PGR_WAIT_PARKED | PGR_WAIT_INIT, pgr_crmath.h) and "the attempt before this one was rejected" as
+    // a mask, each ONE integer in a vector register: as bools they lived in scalar pairs as lane masks, merged at every loop
+    // header and turned into the gate's ballots through v_cndmask + v_cmp
+    int wait = PGR_WAIT_INIT, m_rejected = 0;
     int nb = 0, ns = 0, n_steps = 0, n_rej = 0;
     int jnext = 0;
     double rnext = 0;
@@ -310,30 +313,36 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
            k70 = 0, k71 = 0, k72 = 0;
     // One trip = one step attempt of every stepping lane, THEN the gate that decides whether the
     // wave services its parked lanes.  (The first trip only runs the gate: every lane starts with
-    // need_init.)  The step comes first so that the common path -- nobody parked -- is the loop's
-    // fall-through: one skipped block and the back-edge are its only taken branches.
+    // PGR_WAIT_INIT.)  The step comes first so that the common path -- nobody parked -- is the loop's
+    // fall-through.  Its only taken branch is the one that closes the trip: what an accepted trip rarely needs (min_step,
+    // the events' near-boundary block, the SciPy-order sample pass, the guards) sits out of line behind wave-uniform tests.
     do {
-        bool run, pend;
+        bool run, pend, go_on;
         unsigned long long pm;
         // inner loop: step attempts while no lane is waiting for service (the common case: its
         // only taken branch is its own back-edge)
         do {
-        trips++;
+        // (saturating, HERE: written inside the attempt the counter would be a per-lane value and the guards' test a
+        // per-lane branch; 0x7f000000 is beyond every guard_limit, so the guards stay due once they are)
+        trips = trips < 0x7f000000 ? trips + 1 : trips;
         PGR_STAMP(0);
-        if (status == RUNNING && !parked && !need_init) {
+        if (((status ^ RUNNING) | wait) == 0) {
             // ---- one attempt of RK45._step_impl, SCIPY/rk.py:111-176 ----
             // min_step = 10 ulp(t) <= 10 * 2^-52 max(|x0|, |x1|) =: min_step_bound for every t of the fan: a wave none
             // of whose lanes steps below that bound needs neither the clamp nor the "step too small" test (exactly:
             // h_abs >= bound >= min_step makes both no-ops) -- ten instructions of every attempt otherwise
-            bool too_small = false;
+            int m_small = 0;
             if (__builtin_expect(ballot64(h_abs < min_step_bound) != 0, 0)) {
                 double min_step = min_step_of(t);
-                if (!rejected && h_abs < min_step) h_abs = min_step;  // clamp only on entry
-                too_small = h_abs < min_step;
+                if (m_rejected == 0 && h_abs < min_step) h_abs = min_step;  // clamp only on entry
+                const bool too_small = h_abs < min_step;
                 // (RK45 raises "step size too small": the ray is dropped here and now; what the rest of this attempt
                 // does to the lane's state no longer matters, it is not accepted and never steps again)
                 if (too_small) status = PGR_RAY_STEP_TOO_SMALL;
+                m_small = too_small ? -1 : 0;
             }
+            // (1 behind a rejected attempt, MAX_FACTOR otherwise: known before the stages, see pgr_step_factor)
+            const double fac_limit = pgr_factor_limit(m_rejected, MAX_FACTOR);
             double h = h_abs;
             double t_new = t + h;
             if ((t_new - t_bound) > 0) t_new = t_bound;
@@ -358,25 +367,20 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
             // power is not a number: err = 0 or below the fp32 range of its seed (the true power is
             // huge: MAX_FACTOR, SCIPY/rk.py:153-154), err = inf or NaN (MIN_FACTOR, as np.max / Python's
             // max(MIN_FACTOR, nan) give)
-            const bool accepted = !too_small && (error_norm < 1);
-            const bool reject = !too_small && !accepted;
+            // The decisions travel as masks in vector registers (pgr_crmath.h): "error_norm < 1" is the sign word of
+            // fmin(error_norm, 2) - 1 -- exact for every double, NaN (not accepted) included --, the factor's two min / max and
+            // its select are fmin / fmax and two v_bfi_b32, the counters add the masks.  A compare -> condition register ->
+            // v_cndmask link costs a lone wave ~17 cycles, and three of them sat between the power and h_abs.
+            const int m_acc = pgr_mask_lt_const(error_norm, 1.0, 2.0) & ~m_small;
+            const int m_rej = ~(m_acc | m_small);
             const double pw = SAFETY * pow_m02(error_norm, POW_FIFTH, POW_KLN2);
-            double fac_acc = (pw < MAX_FACTOR) ? pw : MAX_FACTOR;
-            fac_acc = (rejected && !(fac_acc < 1)) ? 1.0 : fac_acc;
-            const double fac_rej = (pw > MIN_FACTOR) ? pw : MIN_FACTOR;
-            h_abs = h_abs * (accepted ? fac_acc : fac_rej);
-            rejected = reject;
-            n_rej += reject ? 1 : 0;
-            // the two step-count guards: no lane has made more attempts than the wave has made trips
-            const bool guards_due = trips > guard_limit;
-            if (__builtin_expect(guards_due, 0)) {
-                const bool over = (n_rej + n_steps) > attempt_limit;
-                status = (reject & over) ? PGR_RAY_MAX_STEPS : status;
-                trips = trips < 0x7f000000 ? trips : 0x7f000000;   // (entered on every trip from here on: the counter cannot wrap)
-            }
+            h_abs = h_abs * pgr_step_factor(m_acc, pw, fac_limit, MIN_FACTOR);
+            m_rejected = m_rej;
+            n_rej -= m_rej;
             PGR_STAMP(16);
 
-            if (accepted) {
+            int m_committed = 0;
+            if (m_acc != 0) {
                 n_steps++;
                 // events at the new point, SCIPY/ivp.py:671-675 (c at (t_new, y_new) is the FSAL lookup)
                 unsigned g_new = C.events(t_new, n1, n2, c_new);
@@ -394,14 +398,18 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
                 if (active) {
                     // park: the step is located, truncated and bounced in the next service phase, from (t, y, f),
                     // pk_tnew and this attempt's stage values (K3 ... K7 stay in this lane's registers: KEEPK)
-                    parked = true;
+                    wait |= PGR_WAIT_PARKED;
                     pk_active = active;
                     pk_tnew = t_new;
                 } else {
                     // ---- _interpolate_ray, streamed (REF/launch_rays.py:763-772, Q5): samples of the
                     // segment slice [idx1, idx2) that this step's quartic owns ----
+                    // The SciPy-order pass is rare (a segment's first step, PGR_EXACT_SAMPLES): behind ONE wave-uniform test,
+                    // out of line -- as the second arm of a per-lane if / else its skip was a taken branch on every trip
+                    // that emits samples (~80 cycles for a lone wave).  The two passes serve disjoint lanes.
                     if (want_samples) {
-                        if (scipy_order) {
+                        if (__builtin_expect(exact_samples || ballot64(rnext < t) != 0, 0)) {
+                          if (scipy_order) {
                             PGR_FORM_Q();
                             while (jnext < S - 1 && rnext <= t_new) {
                                 double o0, o1, o2;
@@ -410,7 +418,9 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
                                 jnext++;
                                 rnext = G.at(jnext);
                             }
-                        } else {
+                          }
+                        }
+                        if (!scipy_order) {
                             // The same quartic summed stage-major, y_old + h * sum_j K_j b_j(xi) with
                             // b_j(xi) = sum_k P[j][k] xi^(k+1), in FMAs: no Q = K.T @ P to form (a third
                             // of the work) and a few ulp from SciPy's summation order.  Output samples
@@ -447,18 +457,35 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
                     t = t_new; y0 = n0; y1 = n1; y2 = n2;
                     f0 = k70; f1 = k71; f2 = k72;
                     // (selects, not a skipped block: a taken branch costs more than these four instructions)
-                    status = ((t - t_bound) >= 0) ? PGR_RAY_OK : status;  // SCIPY/base.py:197
-                    if (__builtin_expect(guards_due, 0))
-                        status = (status == RUNNING && n_steps > max_steps32) ? PGR_RAY_MAX_STEPS : status;
+                    // (PGR_RAY_OK is 0: one v_and with the mask of "t has not reached t_bound", pgr_mask_reached)
+                    static_assert(PGR_RAY_OK == 0, "the status select below is an AND");
+                    status &= ~pgr_mask_reached(t - t_bound);  // SCIPY/base.py:197
+                    m_committed = -1;
                 }
                 PGR_STAMP(18);
             }
+            // the two step-count guards: no lane has made more attempts than the wave has made trips, so ONE wave-uniform
+            // test of the trip count, behind the attempt, serves both -- the rejected lanes' (attempts) and the committed
+            // lanes' (accepted steps, after the test for t_bound as before); a rejected lane takes no part in the block above
+            if (__builtin_expect(trips > guard_limit, 0)) {
+                const bool over = (n_rej + n_steps) > attempt_limit;
+                status = (m_rej != 0 && over) ? PGR_RAY_MAX_STEPS : status;
+                status = (m_committed != 0 && status == RUNNING && n_steps > max_steps32) ? PGR_RAY_MAX_STEPS : status;
+            }
         }
         PGR_STAMP(19);
+        // the gate's two questions -- anybody waiting for the service, anybody running -- one ballot each, each ONE
+        // compare of a vector register with zero, both asked here: folded into the lane masks of other compares, or asked
+        // in a block of its own, a ballot goes through v_cndmask + v_cmp again (hence the empty asm and the `&`)
+        int pending = pgr_lane_pending(status, wait), running = status;
+        asm volatile("" : "+v"(pending), "+v"(running));
+        pm = ballot64(pending != 0);
+        const unsigned long long rm = ballot64(running < 0);
+        go_on = (pm == 0) & (rm != 0);
+        } while (go_on);
+        static_assert(RUNNING == -1, "the gate takes the sign of the status for \"running\"");
         run = (status == RUNNING);
-        pend = run && (parked || need_init);
-        pm = ballot64(pend);
-        } while (pm == 0 && ballot64(run) != 0);
+        pend = run && wait != 0;
         // keep ONE exit of the trip loop: without this the compiler threads "left with pm != 0" straight
         // to the gate and gives the loop two exits, whose unification costs the common path two more
         // taken branches per trip
@@ -505,8 +532,8 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
                     if (save) svc_inv_dsave = as.inv_dsave;
                 }
 #define PGR_SVC(batched_, lazy_) (SVC_BATCH ? (batched_) : (lazy_))
-                if (pend && parked) {
-                    parked = false;
+                if (pend && (wait & PGR_WAIT_PARKED)) {
+                    wait &= ~PGR_WAIT_PARKED;
                     const unsigned active = pk_active;
                     // the parked attempt: same t, y, f and h = t_new - t as when it ran
                     const double t_new = pk_tnew, h = t_new - t;
@@ -877,7 +904,7 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
                                 else {
                                     // (theta_b = -theta at the surface and on a flat floor: the sine of minus an arcsine, cheaply)
                                     y2 = fdiv(pgr_cr_sin_near_minus_asin(theta_b * (M_PI / 180.0), pc_b, A_b), c);
-                                    need_init = true;
+                                    wait |= PGR_WAIT_INIT;
                                     if constexpr (LOG) {
                                         // the bounce log: event e = n_bott + n_surf before this bounce was counted; a
                                         // bounce that drops the ray (backwards, bottom angle out of range) is not logged
@@ -900,7 +927,7 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
                 }
                 PGR_SSTAMP(13);   // new slowness (sine), end of the bounce block
                 if (save && SVC_BATCH) asm volatile("" : "+s"(svc_inv_dsave));
-                if (status == RUNNING && need_init) {
+                if (status == RUNNING && (wait & PGR_WAIT_INIT)) {
                     // ---- fresh solve_ivp: RK45.__init__ (SCIPY/rk.py:84-104) ----
                     double c;
                     C.rhs(t, y1, y2, f0, f1, f2, c);
@@ -930,8 +957,8 @@ pgr_fan_kernel(const EnvDev* __restrict__ env_p, typename FanKernelArgs<LOG>::ty
                     if (interval < h_abs) h_abs = interval;
                     // g = [event(t0, y0) ...], SCIPY/ivp.py:649
                     g = C.events(t, y1, y2, c);
-                    rejected = false;
-                    need_init = false;
+                    m_rejected = 0;
+                    wait &= ~PGR_WAIT_INIT;
                     if (save) {
                         jnext = G.nearest(t, PGR_SVC(svc_inv_dsave, as.inv_dsave));
                         rnext = G.at(jnext);
