@@ -589,6 +589,10 @@ int pgr_boundary_loss_device(pgr_env* env, const double* bx, const double* bp, c
  * of this ABI, stated in a file of its own beside this one. ---- */
 #include "pgr_beam_arrivals.h"
 
+/* ---- Vertical-array beamforming, the time-angle response from the elements' arrival lists:
+ * pgr_array_response_device.  Part of this ABI, stated in a file of its own beside this one. ---- */
+#include "pgr_array.h"
+
 /* What this build of the library is: whether the instruction-layout pass of the build was applied
  * ("relaid: 502 -> 31 straddles ..." or "plain hipcc") and which arithmetic variant was compiled.
  * bench.py puts it into its JSON line so that a measured number names the binary it came from. */

@@ -495,14 +495,15 @@ def _arrival_terms(f, cols, profile, boundary, counts, lag=None):
     return offsets, tube, w, T, I, qa, col
 
 
-def _to_host(f, cols, re, im):
-    """re / im (R, n, m) on the device -> complex128 (R, n, m) on the host, re then im, the source's own columns NaN"""
+def _to_host(f, cols, re, im, axis=1):
+    """re / im (R, n, m) on the device -> complex128 (R, n, m) on the host, re then im, the source's own columns NaN (`axis`:
+    the axis of the n columns when it is not 1)"""
     import torch
     at_source = np.flatnonzero(np.abs(np.asarray(f.x)[cols] - f.x[0]) == 0)
     if len(at_source):                                                # the source's own column, as pressure_field has it
         idx = torch.from_numpy(at_source).to(f.dev)
-        re[:, idx, :] = math.nan
-        im[:, idx, :] = math.nan
+        re.index_fill_(axis, idx, math.nan)
+        im.index_fill_(axis, idx, math.nan)
     out = np.empty(tuple(re.shape), dtype=np.complex128)
     out.real = re.cpu().numpy()
     out.imag = im.cpu().numpy()

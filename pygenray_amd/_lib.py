@@ -115,7 +115,7 @@ def read_abi(header):
     return paths, by_header, constants
 
 
-# (pgr.h first, then the products that came with a header of their own, DESIGN.md sections 16-21; PROTOTYPES: what load() binds)
+# (pgr.h first, then the products that came with a header of their own, DESIGN.md sections 16-22; PROTOTYPES: what load() binds)
 HEADERS, HEADER_PROTOTYPES, _CONSTANTS = read_abi(HEADER)
 PROTOTYPES = {fn: proto for protos in HEADER_PROTOTYPES.values() for fn, proto in protos.items()}
 globals().update(_CONSTANTS)   # PGR_TERMINATE_BACKWARDS, PGR_SAMPLE_MAJOR, ... PGR_OPT_D2H_REGISTER
@@ -917,6 +917,17 @@ def signal_phi_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, phi_pt
     (include/pgr_reflection.h); phi 0 is refused."""
     _signal("_phi", device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, (phi_ptr,), tstart_ptr, frequency, inv_sigma, dt, n_times,
             re_ptr, im_ptr, stream)
+
+
+def array_response_sum(device, offsets_ptr, n_elements, n_cols, t_ptr, i_ptr, q_ptr, phi_ptr, delay_ptr, weight_ptr, tstart_ptr,
+                       frequency, inv_sigma, dt, n_times, n_looks, re_ptr, im_ptr, stream=0):
+    """pgr_array_response_device on raw device pointers (ints; q / phi 0: absent): re / im [n_cols][n_looks][n_times] = the
+    delay-and-sum of the arrivals T / I / q / phi of the groups g = j * n_cols + c over the n_elements elements j, with the
+    delays delay[g][n_looks] and the weights weight[g], at the times tstart[c] + n dt; see include/pgr_array.h.  (Named
+    after what it does, not `..._device`: it has no fan-handle twin.)"""
+    check(load().pgr_array_response_device(
+        int(device), offsets_ptr, int(n_elements), int(n_cols), t_ptr, i_ptr, q_ptr or None, phi_ptr or None, delay_ptr,
+        weight_ptr, tstart_ptr, float(frequency), float(inv_sigma), float(dt), int(n_times), int(n_looks), re_ptr, im_ptr, stream))
 
 
 def _spectrum(suffix, device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, phi, l_ptr, tred_ptr, freq, alpha, re_ptr, im_ptr,

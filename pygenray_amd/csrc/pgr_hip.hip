@@ -64,4 +64,5 @@
 #include "pgr_beam_arrivals.h"  // the terms of that sum listed as arrivals: pgr_fan_beam_arrival_counts_w, pgr_fan_beam_arrivals_w, ..._device_w
 #include "pgr_signal.h"         // received time series of a Gaussian pulse from the arrivals: pgr_signal_device
 #include "pgr_reflect.h"        // the coherent sums with a lag per arrival (complex bottom reflection): pgr_fan_pressure_phi, pgr_signal_device_phi, ...
+#include "pgr_array.h"          // vertical-array beamforming, delay-and-sum over the arrivals (pgr_signal.h's helpers): pgr_array_response_device
 #include "pgr_spectrum.h"       // transfer function of the arrivals over a frequency band: pgr_spectrum_device

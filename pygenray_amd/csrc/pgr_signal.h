@@ -69,11 +69,11 @@ __global__ void __launch_bounds__(64) pgr_sig_sum(SigArgs s)
 #undef SIG_PHI
 }
 
-// both entries: the checks, then `sum` (pgr_sig_sum, or with phi pgr_sig_sum_phi) over (group, tile of samples)
-template <typename... Extra>
-static int sig_run(const char* who, int device, const int64_t* offsets, int64_t n_groups, const double* T, const double* I,
-                   const int32_t* q, const double* tstart, double frequency, double inv_sigma, double dt, int32_t n_times,
-                   double* re, double* im, void* stream, void (*sum)(SigArgs, Extra...), Extra... extra)
+// the checks of every sum over arrival lists at time samples (the entries here and pgr_array_response_device) -> 0 and
+// `tiles`, the tiles of SIG_TILE samples, or the failure
+static int sig_check(const char* who, const int64_t* offsets, int64_t n_groups, const double* T, const double* I,
+                     const double* tstart, double frequency, double inv_sigma, double dt, int32_t n_times, const double* re,
+                     const double* im, int64_t* n_tiles)
 {
     if (!offsets || !T || !I || !tstart || !re || !im) return fail(std::string(who) + ": null argument");
     if (n_groups < 1) return fail(std::string(who) + ": n_groups must be >= 1");
@@ -84,6 +84,18 @@ static int sig_run(const char* who, int device, const int64_t* offsets, int64_t 
     if (!std::isfinite(frequency) || frequency < 0.0) return fail(std::string(who) + ": frequency must be finite and >= 0");
     if (!std::isfinite(inv_sigma) || inv_sigma < 0.0) return fail(std::string(who) + ": inv_sigma must be finite and >= 0");
     if (!std::isfinite(dt) || !(dt > 0.0)) return fail(std::string(who) + ": dt must be finite and > 0");
+    *n_tiles = tiles;
+    return 0;
+}
+
+// both entries: the checks, then `sum` (pgr_sig_sum, or with phi pgr_sig_sum_phi) over (group, tile of samples)
+template <typename... Extra>
+static int sig_run(const char* who, int device, const int64_t* offsets, int64_t n_groups, const double* T, const double* I,
+                   const int32_t* q, const double* tstart, double frequency, double inv_sigma, double dt, int32_t n_times,
+                   double* re, double* im, void* stream, void (*sum)(SigArgs, Extra...), Extra... extra)
+{
+    int64_t tiles = 0;
+    if (sig_check(who, offsets, n_groups, T, I, tstart, frequency, inv_sigma, dt, n_times, re, im, &tiles)) return -1;
     HIPCHK(hipSetDevice(device));
     const SigArgs s{offsets, T, I, q, tstart, frequency, inv_sigma, dt, n_times, re, im};
     hipLaunchKernelGGL(sum, dim3((unsigned)n_groups, (unsigned)tiles), dim3(64), 0, (hipStream_t)stream, s, extra...);
