@@ -593,6 +593,10 @@ int pgr_boundary_loss_device(pgr_env* env, const double* bx, const double* bp, c
  * pgr_array_response_device.  Part of this ABI, stated in a file of its own beside this one. ---- */
 #include "pgr_array.h"
 
+/* ---- Band-averaged power, the transfer function's squared magnitude summed over a band:
+ * pgr_band_power_device.  Part of this ABI, stated in a file of its own beside this one. ---- */
+#include "pgr_band.h"
+
 /* What this build of the library is: whether the instruction-layout pass of the build was applied
  * ("relaid: 502 -> 31 straddles ..." or "plain hipcc") and which arithmetic variant was compiled.
  * bench.py puts it into its JSON line so that a measured number names the binary it came from. */

@@ -23,6 +23,7 @@ from .spectrum import transfer_function, received_waveform
 from .beam_arrivals import (beam_arrivals, BeamArrivals, beam_received_signal, beam_transfer_function,
                             beam_received_waveform)
 from .array import steering_delays, array_response, beam_array_response
+from .band import band_intensity, band_transmission_loss, beam_band_intensity, beam_band_transmission_loss
 from .reflection import BottomReflection, fluid_halfspace
 from .host_physics import (derivsrd, bottom_bounce, surface_bounce, ray_bounding_box_event,
                            ray_angle, bilinear_interp, linear_interp, vertical_ray)
@@ -37,7 +38,8 @@ __all__ = ["OceanEnvironment2D", "munk_ssp", "eflat", "eflatinv", "flat_earth_c"
            "travel_time_kernel", "thorp_absorption", "path_length", "path_loss", "boundary_loss", "BounceLog", "caustic_index", "pressure_field",
            "coherent_transmission_loss", "beam_pressure_field", "coherent_beam_transmission_loss", "received_signal", "pulse_sigma", "transfer_function", "received_waveform", "beam_arrivals",
            "BeamArrivals", "beam_received_signal", "beam_transfer_function", "beam_received_waveform", "steering_delays",
-           "array_response", "beam_array_response", "BottomReflection",
+           "array_response", "beam_array_response", "band_intensity", "band_transmission_loss", "beam_band_intensity",
+           "beam_band_transmission_loss", "BottomReflection",
            "fluid_halfspace", "derivsrd", "bottom_bounce",
            "surface_bounce", "ray_bounding_box_event", "ray_angle", "bilinear_interp",
            "linear_interp", "vertical_ray"]

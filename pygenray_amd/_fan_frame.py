@@ -423,14 +423,15 @@ def _per_column(value, n, name, what):
     return v
 
 
-def _check_fits(f, R, n, m, product, entries):
-    """``ValueError`` when re and im, (R, n, m) float64 each, do not fit in the free memory of the frame's device"""
+def _check_fits(f, R, n, m, product, entries, kind="complex"):
+    """``ValueError`` when re and im, (R, n, m) float64 each -- with `kind` "real" one such array -- do not fit in the free
+    memory of the frame's device"""
     import torch
     # re and im on the device; the host copy is made of them one after the other
-    need = 16 * R * n * m
+    need = (16 if kind == "complex" else 8) * R * n * m
     free = torch.cuda.mem_get_info(f.dev)[0]
     if need > free:
-        raise ValueError(f"the {product} needs {need} bytes of device memory ({R} x {n} x {m} complex {entries}) and {free} "
+        raise ValueError(f"the {product} needs {need} bytes of device memory ({R} x {n} x {m} {kind} {entries}) and {free} "
                          f"are free: ask for fewer depths, columns or {entries} per call")
 
 

@@ -115,7 +115,7 @@ def read_abi(header):
     return paths, by_header, constants
 
 
-# (pgr.h first, then the products that came with a header of their own, DESIGN.md sections 16-22; PROTOTYPES: what load() binds)
+# (pgr.h first, then the products that came with a header of their own, DESIGN.md sections 16-23; PROTOTYPES: what load() binds)
 HEADERS, HEADER_PROTOTYPES, _CONSTANTS = read_abi(HEADER)
 PROTOTYPES = {fn: proto for protos in HEADER_PROTOTYPES.values() for fn, proto in protos.items()}
 globals().update(_CONSTANTS)   # PGR_TERMINATE_BACKWARDS, PGR_SAMPLE_MAJOR, ... PGR_OPT_D2H_REGISTER
@@ -953,3 +953,17 @@ def spectrum_phi_device(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, phi_
     float64, every arrival's lag in cycles (include/pgr_reflection.h); phi 0 is refused."""
     _spectrum("_phi", device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, (phi_ptr,), l_ptr, tred_ptr, freq, alpha, re_ptr, im_ptr,
               stream)
+
+
+def band_power_sum(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, phi_ptr, l_ptr, freq, alpha, weights, out_ptr, stream=0):
+    """pgr_band_power_device on raw device pointers (ints; q / phi / l 0: absent) and the HOST sequences freq (Hz), alpha (dB per
+    metre, or None; given exactly when l is) and weights (one per frequency, finite and >= 0): out [n_groups] = the power of the
+    arrivals T / I / q / phi / L of each group [offsets[g], offsets[g + 1]) summed over the band, sum_k weights[k] |H(freq[k])|^2
+    in the order of include/pgr_band.h.  (Named after what it does, not `..._device`: it has no fan-handle twin.)"""
+    al, fr = _profile(alpha, freq, "freq and alpha")
+    _, wf = _profile(None, weights, "weights")
+    if len(wf) != len(fr):
+        raise ValueError("freq and weights must have equal length")
+    check(load().pgr_band_power_device(
+        int(device), offsets_ptr, int(n_groups), t_ptr, i_ptr, q_ptr or None, phi_ptr or None, l_ptr or None, _addr(fr), _addr(al),
+        _addr(wf), len(fr), out_ptr, stream))

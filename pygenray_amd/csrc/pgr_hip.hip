@@ -65,4 +65,5 @@
 #include "pgr_signal.h"         // received time series of a Gaussian pulse from the arrivals: pgr_signal_device
 #include "pgr_reflect.h"        // the coherent sums with a lag per arrival (complex bottom reflection): pgr_fan_pressure_phi, pgr_signal_device_phi, ...
 #include "pgr_array.h"          // vertical-array beamforming, delay-and-sum over the arrivals (pgr_signal.h's helpers): pgr_array_response_device
+#include "pgr_band.h"           // band-averaged power, pgr_spectrum.h's sum reduced over frequency (it includes pgr_spectrum.h first): pgr_band_power_device
 #include "pgr_spectrum.h"       // transfer function of the arrivals over a frequency band: pgr_spectrum_device

@@ -1,5 +1,6 @@
 // pgr_spectrum.h -- the transfer function of a fan's ray-tube arrivals over a band of frequencies: pgr_spectrum_device.
-// (Part of the ONE translation unit pgr_hip.hip, included there last; not a stand-alone header.)
+// (Part of the ONE translation unit pgr_hip.hip, named there last and first included by pgr_band.h, which builds on it; not a
+// stand-alone header.)
 //
 // The quantity.  Groups and arrivals are section 17's: arrival a of group g lies in
 // [off[g], off[g + 1]), in increasing tube order, with its travel time T_a, its intensity I_a and its phase index q_a in
@@ -139,6 +140,26 @@ __global__ void __launch_bounds__(64) pgr_spec_sum_phi(SpecArgs s, const double*
     else spec_sum<false, true>(s, phi);
 }
 
+// what every entry over a band refuses of the arrival lists and the band (`outputs`: whether its other required pointers are
+// all there), before any device work -> 0 with the number of tiles in *tiles, or fail()'s -1
+static int spec_check(const char* who, const int64_t* offsets, int64_t n_groups, const double* T, const double* I,
+                      const double* L, const double* freq, const double* alpha, int32_t n_freq, bool outputs, int64_t* tiles)
+{
+    if (!offsets || !T || !I || !freq || !outputs) return fail(std::string(who) + ": null argument");
+    if ((L != nullptr) != (alpha != nullptr))
+        return fail(std::string(who) + ": L (the arrivals' path lengths) and alpha go together: give both or neither");
+    if (n_groups < 1) return fail(std::string(who) + ": n_groups must be >= 1");
+    if (n_groups > INT32_MAX) return fail(std::string(who) + ": too many groups");
+    if (n_freq < 1) return fail(std::string(who) + ": n_freq must be >= 1");
+    *tiles = ((int64_t)n_freq + SPEC_TILE - 1) / SPEC_TILE;
+    if (*tiles > 65535) return fail(std::string(who) + ": n_freq must be <= " + std::to_string(65535 * SPEC_TILE));
+    for (int32_t k = 0; k < n_freq; k++) {
+        if (!std::isfinite(freq[k]) || freq[k] < 0.0) return fail(std::string(who) + ": freq must be finite and >= 0");
+        if (alpha && (!std::isfinite(alpha[k]) || alpha[k] < 0.0)) return fail(std::string(who) + ": alpha must be finite and >= 0");
+    }
+    return 0;
+}
+
 // both entries: the checks, the frequencies' device copy, then `sum` (pgr_spec_sum, or with phi pgr_spec_sum_phi) over (group,
 // tile of frequencies)
 template <typename... Extra>
@@ -146,19 +167,8 @@ static int spec_run(const char* who, int device, const int64_t* offsets, int64_t
                     const int32_t* q, const double* L, const double* tred, const double* freq, const double* alpha,
                     int32_t n_freq, double* re, double* im, void* stream, void (*sum)(SpecArgs, Extra...), Extra... extra)
 {
-
-    if (!offsets || !T || !I || !tred || !freq || !re || !im) return fail(std::string(who) + ": null argument");
-    if ((L != nullptr) != (alpha != nullptr))
-        return fail(std::string(who) + ": L (the arrivals' path lengths) and alpha go together: give both or neither");
-    if (n_groups < 1) return fail(std::string(who) + ": n_groups must be >= 1");
-    if (n_groups > INT32_MAX) return fail(std::string(who) + ": too many groups");
-    if (n_freq < 1) return fail(std::string(who) + ": n_freq must be >= 1");
-    const int64_t tiles = ((int64_t)n_freq + SPEC_TILE - 1) / SPEC_TILE;
-    if (tiles > 65535) return fail(std::string(who) + ": n_freq must be <= " + std::to_string(65535 * SPEC_TILE));
-    for (int32_t k = 0; k < n_freq; k++) {
-        if (!std::isfinite(freq[k]) || freq[k] < 0.0) return fail(std::string(who) + ": freq must be finite and >= 0");
-        if (alpha && (!std::isfinite(alpha[k]) || alpha[k] < 0.0)) return fail(std::string(who) + ": alpha must be finite and >= 0");
-    }
+    int64_t tiles = 0;
+    if (spec_check(who, offsets, n_groups, T, I, L, freq, alpha, n_freq, tred && re && im, &tiles)) return -1;
     HIPCHK(hipSetDevice(device));
     const hipStream_t st = (hipStream_t)stream;
     // freq and alpha in one stream-ordered allocation, freed behind the launch (as pgr_path.h's profile)
