@@ -593,6 +593,11 @@ int pgr_boundary_loss_device(pgr_env* env, const double* bx, const double* bp, c
  * pgr_array_response_device.  Part of this ABI, stated in a file of its own beside this one. ---- */
 #include "pgr_array.h"
 
+/* ---- Matched-field processing, the Bartlett ambiguity surface from the elements' arrival lists:
+ * pgr_matched_field_device.  Part of this ABI, stated in a file of its own beside this one (named before pgr_band.h, which
+ * stays the last). ---- */
+#include "pgr_match.h"
+
 /* ---- Band-averaged power, the transfer function's squared magnitude summed over a band:
  * pgr_band_power_device.  Part of this ABI, stated in a file of its own beside this one. ---- */
 #include "pgr_band.h"

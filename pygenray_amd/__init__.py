@@ -24,6 +24,7 @@ from .beam_arrivals import (beam_arrivals, BeamArrivals, beam_received_signal, b
                             beam_received_waveform)
 from .array import steering_delays, array_response, beam_array_response
 from .band import band_intensity, band_transmission_loss, beam_band_intensity, beam_band_transmission_loss
+from .match import matched_field, beam_matched_field
 from .reflection import BottomReflection, fluid_halfspace
 from .host_physics import (derivsrd, bottom_bounce, surface_bounce, ray_bounding_box_event,
                            ray_angle, bilinear_interp, linear_interp, vertical_ray)
@@ -39,7 +40,7 @@ __all__ = ["OceanEnvironment2D", "munk_ssp", "eflat", "eflatinv", "flat_earth_c"
            "coherent_transmission_loss", "beam_pressure_field", "coherent_beam_transmission_loss", "received_signal", "pulse_sigma", "transfer_function", "received_waveform", "beam_arrivals",
            "BeamArrivals", "beam_received_signal", "beam_transfer_function", "beam_received_waveform", "steering_delays",
            "array_response", "beam_array_response", "band_intensity", "band_transmission_loss", "beam_band_intensity",
-           "beam_band_transmission_loss", "BottomReflection",
+           "beam_band_transmission_loss", "matched_field", "beam_matched_field", "BottomReflection",
            "fluid_halfspace", "derivsrd", "bottom_bounce",
            "surface_bounce", "ray_bounding_box_event", "ray_angle", "bilinear_interp",
            "linear_interp", "vertical_ray"]

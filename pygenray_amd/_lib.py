@@ -115,7 +115,7 @@ def read_abi(header):
     return paths, by_header, constants
 
 
-# (pgr.h first, then the products that came with a header of their own, DESIGN.md sections 16-23; PROTOTYPES: what load() binds)
+# (pgr.h first, then the products that came with a header of their own, DESIGN.md sections 16-24; PROTOTYPES: what load() binds)
 HEADERS, HEADER_PROTOTYPES, _CONSTANTS = read_abi(HEADER)
 PROTOTYPES = {fn: proto for protos in HEADER_PROTOTYPES.values() for fn, proto in protos.items()}
 globals().update(_CONSTANTS)   # PGR_TERMINATE_BACKWARDS, PGR_SAMPLE_MAJOR, ... PGR_OPT_D2H_REGISTER
@@ -967,3 +967,24 @@ def band_power_sum(device, offsets_ptr, n_groups, t_ptr, i_ptr, q_ptr, phi_ptr, 
     check(load().pgr_band_power_device(
         int(device), offsets_ptr, int(n_groups), t_ptr, i_ptr, q_ptr or None, phi_ptr or None, l_ptr or None, _addr(fr), _addr(al),
         _addr(wf), len(fr), out_ptr, stream))
+
+
+def matched_field_sum(device, offsets_ptr, n_elements, n_cells, t_ptr, i_ptr, q_ptr, phi_ptr, l_ptr, freq, alpha, weights, data,
+                      normalize, out_ptr, stream=0):
+    """pgr_matched_field_device on raw device pointers (ints; q / phi / l 0: absent) and the HOST sequences freq (Hz), alpha (dB
+    per metre, or None; given exactly when l is), weights (one per frequency, finite and >= 0) and data (complex, (n_elements,
+    len(freq)), finite): out [n_cells] = the Bartlett power of the data against the replicas of every cell, formed from the
+    arrivals T / I / q / phi / L of the groups j * n_cells + g over the elements j and summed over the band in the order of
+    include/pgr_match.h; `normalize`: divided by the replicas' squared norm per frequency.  (Named after what it does, not
+    `..._device`: it has no fan-handle twin.)"""
+    al, fr = _profile(alpha, freq, "freq and alpha")
+    _, wf = _profile(None, weights, "weights")
+    if len(wf) != len(fr):
+        raise ValueError("freq and weights must have equal length")
+    d = np.asarray(data, dtype=np.complex128)
+    if d.shape != (int(n_elements), len(fr)):
+        raise ValueError("data must hold one complex value per element and frequency")
+    dr, di = _c(d.real), _c(d.imag)
+    check(load().pgr_matched_field_device(
+        int(device), offsets_ptr, int(n_elements), int(n_cells), t_ptr, i_ptr, q_ptr or None, phi_ptr or None, l_ptr or None,
+        _addr(fr), _addr(al), _addr(wf), _addr(dr), _addr(di), len(fr), int(bool(normalize)), out_ptr, stream))

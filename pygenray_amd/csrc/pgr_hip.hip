@@ -66,4 +66,5 @@
 #include "pgr_reflect.h"        // the coherent sums with a lag per arrival (complex bottom reflection): pgr_fan_pressure_phi, pgr_signal_device_phi, ...
 #include "pgr_array.h"          // vertical-array beamforming, delay-and-sum over the arrivals (pgr_signal.h's helpers): pgr_array_response_device
 #include "pgr_band.h"           // band-averaged power, pgr_spectrum.h's sum reduced over frequency (it includes pgr_spectrum.h first): pgr_band_power_device
+#include "pgr_match.h"          // matched-field processing, that sum folded with the array's data over elements and frequency: pgr_matched_field_device
 #include "pgr_spectrum.h"       // transfer function of the arrivals over a frequency band: pgr_spectrum_device
